@@ -31,20 +31,33 @@ translocation post-pass over all raw CTX rows (grom_amd.shard.merge_rank_outputs
 -- inside the timed step.  The step time is the max over ranks.  There is no
 data-path collective: chromosomes are independent.
 
-The JSON line also carries:
-  identical_to_oracle_full_scale  every timed run's VCF and .ctx.vcf rows
-                  against the oracle's on the same full-scale genome (sha256
-                  of the non-header rows, tests/golden/oracle_genome_s100.json;
-                  each step writes its own files, hashed after the timed
-                  region: oracle_full_scale.identical_runs "k/K");
-  footprint_rank0 the run's peak device memory (the CLI's footprint line);
-and (rank 0, N=1):
+A plain run does what the headline figure needs and no more: the genome (the
+first run writes it, about two minutes of the generator for 20 GB, and keeps
+it for the following ones, see genome_files: "genome_kept" in the line says
+whether this run found it), the warmup runs, the timed runs, the result line
+-- value, ms_per_step, the last run's footprint and decode lines, and
   roofline        the pileup kernel (k_scan_tile) in the timed whole runs:
                   algorithmic bytes of every launch (read records, CIGAR,
                   packed bases + qualities, reference, caf arrays)
                   / the launches' HIP-event durations, against 8 TB/s HBM;
                   SURVEY 8(d)'s 158.8 B/base model beside it; PMC traffic from
-                  profiles/pmc_genome_30x.json;
+                  profiles/pmc_genome_30x.json.
+--dump-outputs DIR adds the last timed run's rows as arrays (DIR/vcf_rows.npy,
+DIR/ctx_rows.npy: contig, POS, allele codes and every number of the INFO and
+sample columns, of a fixed seeded sample of at most 200,000 rows and 52 MB
+(ctx: 8 MB) in file order, all of them where they fit; DIR/*_row_counts.npy:
+rows per contig and in all); the generator is seeded, so the same arguments
+give the same inputs.
+
+With --full the JSON line also carries:
+  identical_to_oracle_full_scale  every timed run's VCF and .ctx.vcf rows
+                  against the oracle's on the same full-scale genome (sha256
+                  of the non-header rows, tests/golden/oracle_genome_s100.json;
+                  each step writes its own files, hashed after the timed
+                  region: oracle_full_scale.identical_runs "k/K");
+and (rank 0, N=1):
+  roofline.alone  the pileup kernel by itself on the largest chromosome (from
+                  the device-resident leg);
   device_resident the same genome generated on the host (grom_synth_chrom_stream:
                   each chromosome as the BAM's serial stream hands it to its
                   scan) and kept in HBM, scanned with two chromosomes in flight:
@@ -68,6 +81,7 @@ import sys
 import tempfile
 import threading
 import time
+import zlib
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
@@ -163,6 +177,123 @@ def write_genome(work, knobs, lengths, names):
     bam = prefix + ".bam"
     log(f"genome BAM written: {sum(lengths) / 1e9:.3f} Gb, {os.path.getsize(bam) / 1e9:.2f} GB in {dt:.1f} s")
     return bam, prefix + ".fa", dt
+
+
+def genome_cache_dir():
+    """Where generated inputs are kept from one bench run to the next
+    (GROM_BENCH_CACHE; empty: not kept, every run generates its own)."""
+    return os.environ.get("GROM_BENCH_CACHE", os.path.join(REPO, "build", "bench_data"))
+
+
+def genome_files(work, knobs, lengths, names, label):
+    """The workload's BAM + BAI + FASTA in `work`: links to the kept copy
+    (genome_cache_dir()/<label>_<key>, generated on first use; the key is of
+    the generator binary and its arguments),
+    so that a run does not spend two minutes writing 20 GB it wrote before.
+    One copy per label (workload and scale): writing a new one removes the
+    label's copies under other keys (an older generator's); copies for other
+    scales stay until build/bench_data is removed (`make clean`).
+    The side files a run writes next to them (<bam>.mean, <fasta>.info) stay in
+    `work`, as with a freshly written genome.  (bam, fasta, seconds, kept)"""
+    from grom_amd import SYNTH_BIN
+    cache = genome_cache_dir()
+    if not cache:
+        return write_genome(work, knobs, lengths, names) + (False,)
+    h = hashlib.sha256(open(SYNTH_BIN, "rb").read())
+    h.update(json.dumps([synth_args(knobs, lengths), names]).encode())
+    kept = os.path.join(cache, f"{label}_{h.hexdigest()[:16]}")
+    dt, had = 0.0, os.path.isdir(kept)
+    if not had:
+        tmp = f"{kept}.tmp{os.getpid()}"
+        try:
+            shutil.rmtree(tmp, ignore_errors=True)
+            os.makedirs(tmp)
+            _, _, dt = write_genome(tmp, knobs, lengths, names)
+            with open(os.path.join(tmp, "genome.synth_s"), "w") as f:
+                f.write(f"{dt:.1f}\n")
+            try:
+                os.rename(tmp, kept)
+            except OSError:  # another run finished the same genome meanwhile
+                if not os.path.isdir(kept):
+                    raise
+            for d in os.listdir(cache):
+                if d.startswith(label + "_") and d != os.path.basename(kept) and ".tmp" not in d:
+                    shutil.rmtree(os.path.join(cache, d), ignore_errors=True)
+        except (OSError, RuntimeError) as e:
+            shutil.rmtree(tmp, ignore_errors=True)
+            log(f"cannot keep the genome under {cache} ({e}): written for this run only")
+            return write_genome(work, knobs, lengths, names) + (False,)
+        finally:
+            shutil.rmtree(tmp, ignore_errors=True)
+    else:
+        dt = float(open(os.path.join(kept, "genome.synth_s")).read())  # (what writing it took)
+        log(f"genome BAM from {kept}")
+    for f in os.listdir(kept):
+        os.symlink(os.path.join(kept, f), os.path.join(work, f))
+    return os.path.join(work, "genome.bam"), os.path.join(work, "genome.fa"), dt, had
+
+
+_NUM = re.compile(r"[-+]?\d+(?:\.\d+)?(?:[eE][-+]?\d+)?")
+_SYMBOLIC = {"<DEL>": -1.0, "<DUP>": -2.0, "<INV>": -3.0, "<INS>": -4.0, "<CNV>": -5.0, "<CTX>": -6.0}
+# --dump-outputs: at most 200,000 rows per file, and at most DUMP_BYTES of row
+# arrays per file -- 60 MB together, whatever the two files hold
+DUMP_ROWS = 200_000
+DUMP_BYTES = {"vcf": 52_000_000, "ctx": 8_000_000}
+
+
+def allele_code(a):
+    """An allele as a number: a base string in base 6 over ".ACGTN" (its first
+    20 characters), a symbolic allele as a small negative, anything else by
+    its CRC."""
+    if a in _SYMBOLIC:
+        return _SYMBOLIC[a]
+    v = 0
+    for ch in a[:20].upper():
+        d = ".ACGTN".find(ch)
+        if d < 0:
+            return -float(1000 + zlib.crc32(a.encode()))
+        v = v * 6 + d
+    return float(v)
+
+
+def rows_as_array(path, names, limit, max_bytes):
+    """A VCF's rows as float64 [rows, 6 + W]: contig index, POS, REF and ALT
+    codes, the row's number in the file, then every number of the QUAL, FILTER,
+    INFO and sample columns in order (their count, then the values, zero-padded
+    to W, the most any written row has: none is cut off); beside it the rows
+    per contig and in all.  More rows than `limit`, or than fit in
+    `max_bytes`: a fixed seeded sample of them, in file order."""
+    import numpy as np
+    idx = {n.lower(): i for i, n in enumerate(names)}
+    rows = [ln for ln in open(path) if not ln.startswith("#")]
+    per = np.zeros(len(names) + 1, dtype=np.float64)
+    for ln in rows:
+        per[idx.get(ln[:ln.index("\t")].lower(), len(names))] += 1
+    pick = np.random.default_rng(20260101).permutation(len(rows))[:limit]
+    parsed = []
+    for i in pick:
+        f = rows[i].rstrip("\n").split("\t")
+        nums = [float(x) for x in _NUM.findall(" ".join(f[5:8] + f[9:]))]
+        parsed.append([idx.get(f[0].lower(), -1), float(f[1]), allele_code(f[3]), allele_code(f[4]), float(i),
+                       float(len(nums))] + nums)
+    width = max((len(r) for r in parsed), default=6)
+    keep = min(len(parsed), max_bytes // (8 * width))  # (a prefix of the seeded permutation: still a sample)
+    out = np.zeros((keep, width), dtype=np.float64)
+    for j, k in enumerate(np.argsort(pick[:keep], kind="stable")):
+        out[j, :len(parsed[k])] = parsed[k]
+    return out, np.append(per, len(rows))
+
+
+def dump_outputs(dest, vcf, names):
+    """--dump-outputs: what the last timed step wrote (its VCF and .ctx.vcf,
+    the files a caller of the CLI receives) as float64 arrays."""
+    import numpy as np
+    os.makedirs(dest, exist_ok=True)
+    for name, path in (("vcf", vcf), ("ctx", vcf[:-4] + ".ctx.vcf")):
+        rows, counts = rows_as_array(path, names, DUMP_ROWS, DUMP_BYTES[name])
+        np.save(os.path.join(dest, f"{name}_rows.npy"), rows)
+        np.save(os.path.join(dest, f"{name}_row_counts.npy"), counts)
+        log(f"{name}: {int(counts[-1])} rows, {rows.shape[0]} x {rows.shape[1]} written to {dest}")
 
 
 def cli_env(extra=None):
@@ -418,8 +549,14 @@ def main():
     ap.add_argument("--workload", choices=["genome", "chrom"], default="genome",
                     help="genome: configs[2]/[3] human-shape 3.09 Gb genome; chrom: configs[1] 100 Mb chromosome")
     ap.add_argument("--scale", type=float, default=1.0, help="scale every contig length (tests / quick runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-resident", action="store_true", help="skip the device-resident leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: every step's rows against the oracle's digest, the "
+                         "device-resident leg (and the roofline's kernel-alone figure), the CPU baseline and the "
+                         "concordance run.  Without it: set-up, warm-up, the timed steps, the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's VCF and .ctx.vcf rows as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and concordance")
+    ap.add_argument("--no-resident", action="store_true", help="--full without the device-resident leg")
     ap.add_argument("--resident-steps", type=int, default=2)
     ap.add_argument("--inflight", type=int, default=2, help="resident leg: chromosome scans in flight per GPU")
     ap.add_argument("--budget-s", type=float, default=540.0,
@@ -428,6 +565,16 @@ def main():
     args = ap.parse_args()
     t_start = time.perf_counter()
 
+    genome = args.workload == "genome"
+    if genome:
+        knobs, flags = C3, list(GENOME_FLAGS)
+        names = [n for n, _ in GRCH38]
+        lengths = [max(int(L * args.scale), 1_000_000) for _, L in GRCH38]
+    else:
+        knobs, flags = C2, []
+        names = ["chr1"]
+        lengths = [max(int(100_000_000 * args.scale), 1_000_000)]
+    total = sum(lengths)
     import torch
     import torch.distributed as dist
 
@@ -448,6 +595,10 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
 
     import grom_amd
+    # the HIP library every step's CLI process runs on: not built, not loadable
+    # or without this rank's GPU is an error here, before any run
+    if grom_amd.lib().grom_device_count() <= local:
+        raise RuntimeError(f"no GPU {local} for the HIP library: {grom_amd.last_error()}")
     from grom_amd.shard import all_gather_objects, assign_chromosomes, max_over_ranks, merge_rank_outputs_parallel
 
     def barrier():
@@ -455,16 +606,6 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    genome = args.workload == "genome"
-    if genome:
-        knobs, flags = C3, list(GENOME_FLAGS)
-        names = [n for n, _ in GRCH38]
-        lengths = [max(int(L * args.scale), 1_000_000) for _, L in GRCH38]
-    else:
-        knobs, flags = C2, []
-        names = ["chr1"]
-        lengths = [max(int(100_000_000 * args.scale), 1_000_000)]
-    total = sum(lengths)
     shares = assign_chromosomes(lengths, world)
     mine = shares[rank]
 
@@ -473,7 +614,7 @@ def main():
     if rank == 0:
         shutil.rmtree(work, ignore_errors=True)
         os.makedirs(work, exist_ok=True)
-        bam, fa, t_synth = write_genome(work, knobs, lengths, names)
+        bam, fa, t_synth, genome_kept = genome_files(work, knobs, lengths, names, f"{args.workload}_s{args.scale:g}")
     barrier()
     bam, fa = os.path.join(work, "genome.bam"), os.path.join(work, "genome.fa")
 
@@ -553,7 +694,7 @@ def main():
     launches = [(launch_bytes(s["reads"], s["cigar_ops"], s["bases"], s["len"]), s["ms_pileup"], s["len"])
                 for s in stats.values()]
     resident, alone = None, None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         remaining = args.budget_s - (time.perf_counter() - t_start)
         est = 0.55 * (t_synth if genome else 30.0) + 20.0  # host generation (no compression) + passes
         if args.no_resident:
@@ -568,16 +709,19 @@ def main():
                 f"{resident['rows_identical_to_whole_run']}/{resident['ctx_identical_to_whole_run']}")
     if rank == 0:
         cpu = conc = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             with tempfile.TemporaryDirectory() as d:
                 cpu, conc = cpu_baseline_and_concordance(d, knobs, flags)
         # every timed step's rows against the oracle's full-scale digest
         # (after the timed region; each step wrote its own files)
         final_of = [outs(k)[0] if world == 1 else outs(k)[1] for k in range(args.steps)]
         final_vcf = final_of[-1]
-        n_rows, _ = rows_digest(final_vcf)
-        full = None
-        if genome and args.scale == 1.0:
+        with open(final_vcf, "rb") as f:
+            n_rows = sum(1 for ln in f if not ln.startswith(b"#"))
+        full = full_steps_agree = None
+        if not args.full:
+            pass  # (the comparisons below read every step's rows again: --full)
+        elif genome and args.scale == 1.0:
             per = [oracle_full_scale(v, v[:-4] + ".ctx.vcf") for v in final_of]
             full = per[-1]
             if full is not None:
@@ -599,6 +743,7 @@ def main():
             "value": round(value, 3),
             "unit": "Mbases/s",
             "n_gpus": world,
+            "full": args.full,
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -614,7 +759,7 @@ def main():
                                  "SV/INDEL rows, CTX records, read-depth CNV path + rows), VCF + CTX post-pass",
                 "genome_bases": total, "chromosomes": len(lengths), "chromosomes_rank0": len(mine),
                 "coverage": knobs["coverage"], "read_len": READ_LEN, "flags": " ".join(flags),
-                "bam_bytes": os.path.getsize(bam), "synth_s": round(t_synth, 1),
+                "bam_bytes": os.path.getsize(bam), "synth_s": round(t_synth, 1), "genome_kept": genome_kept,
                 "run_s": [round(x, 3) for x in runs],
                 "vcf_rows": n_rows,
                 "host_cpus": cpus, "decode": "device (GPU inflate + parse)" if dec and dec[-1].startswith("device") else "host threads",
@@ -640,8 +785,10 @@ def main():
             "concordance": conc,
             "device_resident": resident,
         }
-        if full is None and not (genome and args.scale == 1.0):
+        if args.full and full is None and not (genome and args.scale == 1.0):
             line["steps_rows_identical"] = full_steps_agree
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, final_vcf, names)
         print(json.dumps(line), flush=True)
     barrier()
     for k in range(args.steps):
