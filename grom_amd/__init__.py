@@ -127,6 +127,7 @@ _SIGS = {
     "grom_out_free": (None, [C.POINTER(Out)]),
     "grom_fmt_selftest": (C.c_int64, [C.c_int64, C.c_uint64]),
     "grom_bai_build": (C.c_int, [C.c_char_p]),
+    "grom_bai_build_device": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int64)]),
     "grom_bai_summary": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64)]),
     "grom_bai_selftest": (C.c_int64, [C.c_char_p, C.c_int64, C.c_uint64, C.POINTER(C.c_int64)]),
     "grom_upload": (C.c_int, [C.c_int, C.POINTER(Chrom), C.POINTER(Reads), C.POINTER(Chrom), C.POINTER(Reads)]),
@@ -189,6 +190,19 @@ def last_error() -> str:
 def check(rc: int, what: str) -> None:
     if rc != 0:
         raise RuntimeError(f"{what} failed ({rc}): {last_error()}")
+
+
+BAI_BUILD_COUNTERS = ("records", "blocks", "pieces", "chunks_rewalked", "chunks", "runs", "device_us", "wall_us")
+
+
+def bai_build(bam: str, bai: str = None, device: int = 0) -> dict:
+    """Index `bam` on the GPU `device` into `bai` (default <bam>.bai): the file
+    grom_bai_build writes, byte for byte.  Returns the build's counters; raises
+    with the library's message (a failed build leaves no file)."""
+    out = (C.c_int64 * 8)()
+    rc = lib().grom_bai_build_device(os.fsencode(bam), None if bai is None else os.fsencode(bai), device, out)
+    check(rc, "grom_bai_build_device")
+    return dict(zip(BAI_BUILD_COUNTERS, (int(v) for v in out)))
 
 
 def default_params() -> Params:

@@ -713,6 +713,30 @@ void bai_racc_flush(bai_racc *A) {
     A->in_run = 0;
 }
 
+void bai_racc_add_run(bai_racc *A, uint32_t bin, uint64_t voff_beg, uint64_t voff_end) {
+    acc_chunk(A, bin, voff_beg, voff_end);
+}
+
+void bai_racc_set_span(bai_racc *A, uint64_t off_beg, uint64_t off_end, uint64_t n_mapped, uint64_t n_unmapped) {
+    A->any = 1;
+    A->off_beg = off_beg;
+    A->off_end = off_end;
+    A->n_mapped = n_mapped;
+    A->n_unmapped = n_unmapped;
+}
+
+int bai_racc_set_linear(bai_racc *A, const uint64_t *lin, int32_t n_lin) {
+    free(A->lin);
+    A->lin = NULL;
+    A->n_lin = 0;
+    if (n_lin <= 0) return 0;
+    A->lin = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)n_lin);
+    if (!A->lin) return -1;
+    memcpy(A->lin, lin, sizeof(uint64_t) * (size_t)n_lin);
+    A->n_lin = n_lin;
+    return 0;
+}
+
 static int cmp_bin_acc(const void *a, const void *b) {
     const uint32_t x = ((const bin_acc *)a)->bin, y = ((const bin_acc *)b)->bin;
     return x < y ? -1 : x > y;

@@ -179,6 +179,14 @@ bai_racc *bai_racc_new(void);
 void bai_racc_push(bai_racc *A, int32_t beg, int32_t end, uint64_t voff_beg, uint64_t voff_end, int unmapped);
 void bai_racc_flush(bai_racc *A);
 void bai_racc_free(bai_racc *A);
+/* the same accumulator fed whole runs instead of records (the device builder,
+ * baidev.hip, reduces the records itself): one finished run of records with
+ * one bin, in file order, through the same merge rule as bai_racc_push's runs;
+ * the pseudo-bin's offset span and counts; the linear index (n_lin windows,
+ * UINT64_MAX = no record, copied) */
+void bai_racc_add_run(bai_racc *A, uint32_t bin, uint64_t voff_beg, uint64_t voff_end);
+void bai_racc_set_span(bai_racc *A, uint64_t off_beg, uint64_t off_end, uint64_t n_mapped, uint64_t n_unmapped);
+int bai_racc_set_linear(bai_racc *A, const uint64_t *lin, int32_t n_lin);
 /* R[t] may be NULL (no records); 0 or -1 */
 int bai_write_racc(const char *path, bai_racc **R, int n_ref, uint64_t n_no_coor,
                    uint64_t (*map)(void *ctx, int ref, uint64_t voff), void *ctx);

@@ -66,6 +66,12 @@ int dd_comp_begin(dd_ctx *c, int slot, int64_t comp_len, char *err, int errlen);
 int dd_comp_ring_wait(dd_ctx *c, int ring);
 int dd_comp_chunk(dd_ctx *c, int slot, int ring, const uint8_t *h_buf, int64_t dst_off, int64_t n, char *err, int errlen);
 int dd_comp_end(dd_ctx *c, int slot, int64_t comp_len, char *err, int errlen);
+/* for a decode of its own over a filled slot (the index builder, baidev.hip):
+ * the slot's device bytes and their capacity (valid until the slot is filled
+ * again), and `stream` (a hipStream_t) made to wait for the slot's last
+ * dd_comp_end / dd_comp_upload */
+int dd_comp_view(dd_ctx *c, int slot, const uint8_t **d_comp, int64_t *cap);
+int dd_comp_wait_on(dd_ctx *c, int slot, void *stream);
 typedef struct dd_parse_out {
     int64_t n_rec, n_kept, n_drop, n_cig, n_bases, n_auxc;
     int32_t last_pos, last_lq, last_hclip, last_kept;

@@ -1644,6 +1644,18 @@ extern "C" int dd_comp_end(dd_ctx *c, int slot, int64_t comp_len, char *err, int
     return 0;
 }
 
+extern "C" int dd_comp_view(dd_ctx *c, int slot, const uint8_t **d_comp, int64_t *cap) {
+    if (slot < 0 || slot >= DD_SLOTS || !c->dcomp[slot].p) return -1;
+    *d_comp = P<uint8_t>(c->dcomp[slot]);
+    *cap = (int64_t)c->dcomp[slot].cap;
+    return 0;
+}
+
+extern "C" int dd_comp_wait_on(dd_ctx *c, int slot, void *stream) {
+    if (slot < 0 || slot >= DD_SLOTS) return -1;
+    return hipStreamWaitEvent((hipStream_t)stream, c->cev[slot], 0) == hipSuccess ? 0 : -1;
+}
+
 // A DBuf grown to `bytes` keeping its first `keep` bytes (a copy on `st`)
 static int dgrow_keep(DBuf &b, size_t bytes, size_t keep, hipStream_t st) {
     if (b.cap >= bytes) return 0;

@@ -1654,6 +1654,20 @@ static void on_fatal_trace(int sig) {
     raise(sig);
 }
 
+/* 1 if a file stands where the BAM's index is looked for (<bam>.bai or
+ * <stem>.bai), readable or not */
+static int index_file_present(const char *bam_path) {
+    char path[4096];
+    snprintf(path, sizeof(path), "%s.bai", bam_path);
+    if (access(path, F_OK) == 0) return 1;
+    const size_t n = strlen(bam_path);
+    if (n > 4 && strcmp(bam_path + n - 4, ".bam") == 0) {
+        snprintf(path, sizeof(path), "%.*s.bai", (int)(n - 4), bam_path);
+        if (access(path, F_OK) == 0) return 1;
+    }
+    return 0;
+}
+
 static int cli_run(int argc, char **argv, int force_serial) {
     if (getenv("GROM_SEGV_TRACE")) {
         struct sigaction sa;
@@ -1755,6 +1769,17 @@ static int cli_run(int argc, char **argv, int force_serial) {
             return 1;
         }
         bgzf_close_read(&br);
+    }
+    /* GROM_BUILD_INDEX=1: a BAM with no index file gets one, built on the run's
+     * device (grom_bai_build_device); a file that is there is never replaced */
+    if (getenv("GROM_BUILD_INDEX") && atoi(getenv("GROM_BUILD_INDEX")) != 0 && !index_file_present(S->bam_name)) {
+        int64_t bo[8];
+        if (grom_bai_build_device(S->bam_name, NULL, S->device, bo) != 0) {
+            printf("Could not build the BAM index: %s\n", grom_last_error());
+            goto out_hdr;
+        }
+        printf("built %s.bai on device %d in %.3f s (%lld records, %.3f s on the device)\n", S->bam_name, S->device,
+               (double)bo[7] / 1e6, (long long)bo[0], (double)bo[6] / 1e6);
     }
     if (!bai_loads(S->bam_name)) { printf("Could not open BAM indexing file\n"); goto out_hdr; }
     if (!S->out_name) { printf("ERROR: No output file specified.\n"); goto out_hdr; }

@@ -469,6 +469,16 @@ void grom_batch_release(grom_batch_handle *h);
  * bam_fetch, GROM.c:216-261 and 22128-22138; SAM v1 section 5.2) ---- */
 /* index <bam> into <bam>.bai: 0, or negative */
 int grom_bai_build(const char *bam_path);
+/* the same index, byte for byte, built on `device` (the file read once, its
+ * blocks inflated and its records walked and reduced on the GPU), written to
+ * bai_path (NULL: <bam>.bai) under a temporary name and renamed on success:
+ * a failed build leaves no file.  0, or a negative GROM_E_* code with
+ * grom_last_error() set (GROM_E_NODEV: no such device; GROM_E_ARG: a file
+ * the host builder refuses too -- unsorted, truncated).  out (may be NULL) =
+ * {records, BGZF blocks, pieces, walk chunks walked again, walk chunks, runs,
+ * device time (us, HIP events), wall time (us)}.  GROM_INDEX_PIECE_KB sets
+ * the inflated bytes per piece (default 3145728 = 3 GB). */
+int grom_bai_build_device(const char *bam_path, const char *bai_path, int device, int64_t out[8]);
 /* parse an index file; out = {n_ref, bins, chunks, linear intervals,
  * unplaced-read count or -1 when absent}.  0, or negative */
 int grom_bai_summary(const char *bai_path, int64_t out[5]);
