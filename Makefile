@@ -11,7 +11,7 @@ BINDIR  = grom_amd/bin
 
 HOST_SRC = grom_amd/csrc/bamio.c grom_amd/csrc/stream.c grom_amd/csrc/tables.c grom_amd/csrc/synth.c grom_amd/csrc/hostapi.c grom_amd/csrc/grom_main.c grom_amd/csrc/pdecode.c
 HOST_OBJ = $(patsubst grom_amd/csrc/%.c,build/%.o,$(HOST_SRC)) build/snvfmt.o build/svcall.o build/inflate_host.o build/devmem.o
-DEV_OBJ = build/scan.o build/cnv.o build/sv.o build/ddecode.o build/baidev.o
+DEV_OBJ = build/scan.o build/cnv.o build/sv.o build/ddecode.o build/baidev.o build/fastadev.o
 HDRS = include/grom_amd.h grom_amd/csrc/devmem.h grom_amd/csrc/scan_common.h grom_amd/csrc/bamio.h grom_amd/csrc/stream.h grom_amd/csrc/synth.h grom_amd/csrc/pdecode.h grom_amd/csrc/ddecode.h
 KHDRS = grom_amd/csrc/k_scan_tile.h grom_amd/csrc/device_common.h grom_amd/csrc/snvfmt.h
 
@@ -41,6 +41,11 @@ build/ddecode.o: grom_amd/csrc/ddecode.hip grom_amd/csrc/ddecode.h grom_amd/csrc
 
 # a missing BAM index built on the device (the decoder's inflater and upload path)
 build/baidev.o: grom_amd/csrc/baidev.hip grom_amd/csrc/ddecode.h $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the reference FASTA read on the device, bgzip-compressed or plain (the decoder's inflater)
+build/fastadev.o: grom_amd/csrc/fastadev.hip grom_amd/csrc/ddecode.h $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -87,12 +92,12 @@ oracle:
 # kernel tuning variants, loaded with GROM_AMD_LIB=...:
 #   make variant V=w4 VFLAGS=-DGROM_WAVES_PER_EU=4  ->  grom_amd/lib/variants/libgrom_amd_w4.so
 #   make variant V=q0 VFLAGS=-DGI_QUAD=0            (the inflater's bit reader)
-variant: $(HOST_OBJ) build/sv.o build/baidev.o
+variant: $(HOST_OBJ) build/sv.o build/baidev.o build/fastadev.o
 	@mkdir -p build/variants $(LIBDIR)/variants
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c grom_amd/csrc/scan.hip -o build/variants/scan_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -ffp-contract=off -c grom_amd/csrc/cnv.hip -o build/variants/cnv_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c grom_amd/csrc/ddecode.hip -o build/variants/ddecode_$(V).o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(LIBDIR)/variants/libgrom_amd_$(V).so build/variants/scan_$(V).o build/variants/cnv_$(V).o build/sv.o build/variants/ddecode_$(V).o build/baidev.o $(HOST_OBJ) -lz -lm
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(LIBDIR)/variants/libgrom_amd_$(V).so build/variants/scan_$(V).o build/variants/cnv_$(V).o build/sv.o build/variants/ddecode_$(V).o build/baidev.o build/fastadev.o $(HOST_OBJ) -lz -lm
 
 clean:
 	rm -rf build $(LIBDIR) $(BINDIR)

@@ -162,6 +162,22 @@ _SIGS = {
     "grom_scan_chrom_staged": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(Chrom), C.POINTER(Out), C.POINTER(Stats)]),
     "grom_debug_counts_staged": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(Chrom), C.POINTER(C.c_int32), C.c_void_p,
                                            C.c_int64, C.c_void_p]),
+    # the reference FASTA on the device, bgzip-compressed or plain (fastadev.hip)
+    "grom_fasta_dev_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "grom_fasta_dev_close": (None, [C.c_void_p]),
+    "grom_fasta_dev_is_bgzf": (C.c_int, [C.c_void_p]),
+    "grom_fasta_dev_index": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "grom_fasta_dev_entry": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "grom_fasta_dev_set_index": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_char_p, C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "grom_fasta_dev_load": (C.c_int64, [C.c_void_p, C.c_int, C.c_char_p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "grom_fasta_dev_release": (None, [C.c_void_p, C.c_void_p]),
+    "grom_fasta_dev_times": (None, [C.c_void_p, C.POINTER(C.c_double)]),
+    "grom_fasta_host_index": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.c_char_p, C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "grom_fasta_host_load": (C.c_int64, [C.c_char_p, C.c_int, C.c_char_p, C.c_int64]),
+    "grom_stage_set_ref_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
 }
 
 _lib = None
@@ -203,6 +219,140 @@ def bai_build(bam: str, bai: str = None, device: int = 0) -> dict:
     rc = lib().grom_bai_build_device(os.fsencode(bam), None if bai is None else os.fsencode(bai), device, out)
     check(rc, "grom_bai_build_device")
     return dict(zip(BAI_BUILD_COUNTERS, (int(v) for v in out)))
+
+
+FASTA_NAME_LEN = 50
+FASTA_HOST_ONLY = -100
+FASTA_TIMES = ("read_upload_ms", "inflate_ms", "index_kernels_ms", "load_kernels_ms", "load_d2h_ms", "open_wall_ms",
+               "index_wall_ms", "loads_wall_ms")
+
+
+class FastaHostOnly(RuntimeError):
+    """The device loader's "host only" answer (a NUL byte in the text, or more
+    headers than the host table keeps): the host code has to read the file."""
+
+
+def _fasta_host_index(path):
+    L = lib()
+    p = os.fsencode(path)
+    n = L.grom_fasta_host_index(p, 0, None, None, None, None, None)
+    if n < 0:
+        raise RuntimeError(f"grom_fasta_host_index failed ({n}): {last_error()}")
+    m = C.c_int64(0)
+    names = C.create_string_buffer(FASTA_NAME_LEN * max(n, 1))
+    nl, fp, ln = (C.c_int * max(n, 1))(), (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))()
+    L.grom_fasta_host_index(p, n, C.byref(m), names, nl, fp, ln)
+    ent = [{"name": names.raw[i * FASTA_NAME_LEN:(i + 1) * FASTA_NAME_LEN].split(b"\0")[0].decode("latin-1"),
+            "name_len": nl[i], "file_pos": fp[i], "len": ln[i]} for i in range(n)]
+    return {"n": n, "mappable": m.value, "entries": ent}
+
+
+class FastaDevice:
+    """A FASTA (plain or BGZF) brought to GPU `device` (grom_fasta_dev_*)."""
+
+    def __init__(self, path, device: int = 0):
+        self.h = C.c_void_p()
+        check(lib().grom_fasta_dev_open(os.fsencode(path), device, C.byref(self.h)), "grom_fasta_dev_open")
+
+    def close(self):
+        if self.h:
+            lib().grom_fasta_dev_close(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def bgzf(self) -> bool:
+        return bool(lib().grom_fasta_dev_is_bgzf(self.h))
+
+    def entries(self, n):
+        out = []
+        for i in range(n):
+            name = C.create_string_buffer(FASTA_NAME_LEN)
+            nl, fp, ln, ll = C.c_int(), C.c_int64(), C.c_int64(), C.c_int64()
+            check(lib().grom_fasta_dev_entry(self.h, i, name, C.byref(nl), C.byref(fp), C.byref(ln), C.byref(ll)),
+                  "grom_fasta_dev_entry")
+            out.append({"name": name.raw.split(b"\0")[0].decode("latin-1"), "name_len": nl.value,
+                        "file_pos": fp.value, "len": ln.value, "load_len": ll.value})
+        return out
+
+    def index(self) -> dict:
+        n, m = C.c_int(), C.c_int64()
+        rc = lib().grom_fasta_dev_index(self.h, C.byref(n), C.byref(m))
+        if rc == FASTA_HOST_ONLY:
+            raise FastaHostOnly("the device index pass reports: host only")
+        check(rc, "grom_fasta_dev_index")
+        return {"n": n.value, "mappable": m.value, "entries": self.entries(n.value)}
+
+    def set_index(self, table: dict):
+        ent = table["entries"]
+        n = len(ent)
+        names = b"".join(e["name"].encode("latin-1").ljust(FASTA_NAME_LEN, b"\0") for e in ent)
+        check(lib().grom_fasta_dev_set_index(self.h, n, table["mappable"], names,
+                                             (C.c_int * max(n, 1))(*[e["name_len"] for e in ent]),
+                                             (C.c_int64 * max(n, 1))(*[e["file_pos"] for e in ent]),
+                                             (C.c_int64 * max(n, 1))(*[e["len"] for e in ent])),
+              "grom_fasta_dev_set_index")
+
+    def load_len(self, i: int) -> int:
+        r = lib().grom_fasta_dev_load(self.h, i, None, 0, None)
+        if r == FASTA_HOST_ONLY:
+            raise FastaHostOnly("the device loader reports: host only")
+        if r < 0:
+            check(int(r), "grom_fasta_dev_load")
+        return int(r)
+
+    def load(self, i: int) -> bytes:
+        n = self.load_len(i)
+        buf = C.create_string_buffer(max(n, 1))
+        r = lib().grom_fasta_dev_load(self.h, i, buf, n, None)
+        if r == FASTA_HOST_ONLY:
+            raise FastaHostOnly("the device loader reports: host only")
+        if r < 0:
+            check(int(r), "grom_fasta_dev_load")
+        return buf.raw[:n]
+
+    def times(self) -> dict:
+        ms = (C.c_double * 8)()
+        lib().grom_fasta_dev_times(self.h, ms)
+        return dict(zip(FASTA_TIMES, (float(v) for v in ms)))
+
+
+def fasta_index(path, device: "int | None" = None) -> dict:
+    """The FASTA index (find_genome_length): {"n", "mappable", "entries": [{"name",
+    "name_len", "file_pos", "len"(, "load_len")}]}.  device=None runs the host
+    code (a BGZF file inflated on the host); else the device pass, which raises
+    FastaHostOnly where only the host code can read the file."""
+    if device is None:
+        return _fasta_host_index(path)
+    with FastaDevice(path, device) as f:
+        return f.index()
+
+
+def fasta_load(path, i: int, device: "int | None" = None, host_fallback: bool = True) -> bytes:
+    """Entry i's bytes as the loader keeps them.  device=None runs the host
+    code.  On a device, "host only" takes the host path as the CLI does
+    (host_fallback=False: raises FastaHostOnly)."""
+    if device is not None:
+        try:
+            with FastaDevice(path, device) as f:
+                f.index()
+                return f.load(i)
+        except FastaHostOnly:
+            if not host_fallback:
+                raise
+    L = lib()
+    p = os.fsencode(path)
+    n = L.grom_fasta_host_load(p, i, None, 0)
+    if n < 0:
+        raise RuntimeError(f"grom_fasta_host_load failed ({n}): {last_error()}")
+    buf = C.create_string_buffer(max(n, 1))
+    L.grom_fasta_host_load(p, i, buf, n)
+    return buf.raw[:n]
 
 
 def default_params() -> Params:

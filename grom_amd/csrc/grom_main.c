@@ -185,12 +185,27 @@ typedef struct {
     int fasta_idx;
     int32_t tid;
     char *ref;
+    const void *d_ref; /* the same bytes in device memory (the device FASTA loader's), else NULL */
     long len;
     char name[GROM_MAX_CHR_NAME_LEN + 1];
     char *target; /* BAM name the SA/XP chromosome test compares with (GROM.c:1894-1961, 7431) */
 } chrom_plan;
 
 static int g_plan_only = 0; /* GROM_PLAN_ONLY: report the record plan, no GPU */
+
+/* the device FASTA loader (fastadev.hip) of this run: a BGZF -r by default, a
+ * plain one with GROM_FASTA_DEVICE=1.  One thread at a time uses the handle */
+static grom_fasta_dev *g_fdev = NULL;
+static int g_fdev_device = -1;
+static pthread_mutex_t g_fdev_mu = PTHREAD_MUTEX_INITIALIZER;
+
+static void plan_release_dref(chrom_plan *c) {
+    if (!c->d_ref) return;
+    pthread_mutex_lock(&g_fdev_mu);
+    if (g_fdev) grom_fasta_dev_release(g_fdev, c->d_ref);
+    c->d_ref = NULL;
+    pthread_mutex_unlock(&g_fdev_mu);
+}
 static const char *g_side_base; /* -o name: the -N side files are named after it */
 
 static double clock_gettime_s(void) {
@@ -671,6 +686,7 @@ static void *grom_worker_main(void *arg) {
         if (rc != GROM_OK) snprintf(j->err, sizeof(j->err), "%s: %s", j->cp->name, grom_last_error());
         free(j->cp->ref);
         j->cp->ref = NULL;
+        plan_release_dref(j->cp);
         if (j->has_batch) grom_batch_free(&j->batch);
         if (j->stage && j->pd && !j->stage_released) pd_release_stage(j->pd, j->stage);
         j->stage = NULL;
@@ -704,7 +720,7 @@ typedef struct {
     double t_scans, t_pdclose, t_outputs; /* scans done, decoder closed, outputs written */
     double t_decclose;                     /* the decoder's host side closed */
     pthread_t hip_thr;     /* HIP runtime start-up, beside the header/FASTA/index work */
-    int hip_started;
+    int hip_started, hip_done;
     /* -P n (1..256, GROM.c:21923-21927): every chromosome reads its own
      * target's records (bam_fetch, GROM.c:21051-21064 and the -c children of
      * GROM.c:549-599) -- pd_set_fetch_mode; GROM_P_SERIAL=1 keeps the serial
@@ -828,8 +844,80 @@ static void *hip_init_main(void *arg) {
 }
 
 static void hip_ready(cli_state *S) {
-    if (S->hip_started) pthread_join(S->hip_thr, NULL);
+    if (S->hip_started) {
+        pthread_join(S->hip_thr, NULL);
+        S->hip_done = 1;
+    }
     S->hip_started = 0;
+}
+
+/* The -r file opened.  Plain text: the host table and loader, as ever
+ * (GROM_FASTA_DEVICE=1: the device loader).  BGZF: the device loader
+ * (GROM_FASTA_DEVICE=0, the serial reader and plan-only runs: inflated on the
+ * host).  <fasta>.info is read and written either way; for a BGZF file its
+ * file_pos are offsets in the inflated text.  The device open waits for the
+ * HIP start-up thread. */
+static int cli_fasta_open(cli_state *S, int force_serial) {
+    const int kind = grom_fasta_file_kind(S->fasta_name);
+    const char *fd = getenv("GROM_FASTA_DEVICE"), *ser = getenv("GROM_SERIAL_DECODE");
+    const int serial = force_serial || (ser && atoi(ser) > 0);
+    const int want = (kind == 1 && !(fd && atoi(fd) == 0)) || (kind == 0 && fd && atoi(fd) == 1);
+    if (kind == 2 || !want || serial || g_plan_only) {
+        if (grom_fasta_open_cached(&S->fa, S->fasta_name) != 0) {
+            printf("\nCould not open %s\n", S->fasta_name);
+            if (kind == 2) printf("%s\n", grom_last_error());
+            return -1;
+        }
+        return 0;
+    }
+    S->hip_started = pthread_create(&S->hip_thr, NULL, hip_init_main, &S->device) == 0;
+    memset(&S->fa, 0, sizeof(S->fa));
+    grom_fasta_info_load(&S->fa, S->fasta_name);
+    const long kept = S->fa.n > 0 ? 0 : S->fa.mappable;
+    hip_ready(S);
+    grom_fasta_dev *d = NULL;
+    if (grom_fasta_dev_open(S->fasta_name, S->device, &d) != 0) {
+        printf("\nCould not open %s\n%s\n", S->fasta_name, grom_last_error());
+        return -1;
+    }
+    int rc = 0;
+    if (S->fa.n > 0) {
+        int64_t *fp = malloc(sizeof(int64_t) * S->fa.n), *ln = malloc(sizeof(int64_t) * S->fa.n);
+        for (int i = 0; i < S->fa.n; i++) { fp[i] = S->fa.file_pos[i]; ln[i] = S->fa.len[i]; }
+        rc = grom_fasta_dev_set_index(d, S->fa.n, S->fa.mappable, (const char *)S->fa.names, S->fa.name_len, fp, ln);
+        free(fp);
+        free(ln);
+    } else {
+        int n = 0;
+        int64_t mappable = 0;
+        rc = grom_fasta_dev_index(d, &n, &mappable);
+        if (rc == 0 && grom_fasta_reserve(&S->fa, n) != 0) rc = GROM_E_NOMEM;
+        if (rc == 0) {
+            for (int i = 0; i < n; i++) {
+                int64_t fp = 0, ln = 0;
+                grom_fasta_dev_entry(d, i, S->fa.names[i], &S->fa.name_len[i], &fp, &ln, NULL);
+                S->fa.file_pos[i] = (long)fp;
+                S->fa.len[i] = (long)ln;
+            }
+            S->fa.n = n;
+            S->fa.mappable = (long)mappable + kept;
+            grom_fasta_info_save(&S->fa, S->fasta_name);
+        }
+    }
+    if (rc != 0) { /* "host only", or the device pass failed: the host reads the file */
+        if (rc != GROM_FASTA_HOST_ONLY) fprintf(stderr, "grom: device FASTA loader: %s\n", grom_last_error());
+        fprintf(stderr, "grom: reading %s on the host\n", S->fasta_name);
+        grom_fasta_dev_close(d);
+        grom_fasta_close(&S->fa);
+        if (grom_fasta_open_cached(&S->fa, S->fasta_name) != 0) {
+            printf("\nCould not open %s\n", S->fasta_name);
+            return -1;
+        }
+        return 0;
+    }
+    g_fdev = d;
+    g_fdev_device = S->device;
+    return 0;
 }
 
 #define CLI_FALLBACK 99 /* the streamed path could not be used: read serially */
@@ -1195,6 +1283,18 @@ static char *ref_alloc(long len) {
     return (char *)p;
 }
 
+/* the host loader on a run that reads the FASTA on the device ("host only", a
+ * failed device load): the stream is opened when first needed (a BGZF file is
+ * inflated on the host) and read by one thread at a time */
+static long cli_fasta_host_load(cli_state *S, int fi, char *buf, long cap) {
+    static pthread_mutex_t fmu = PTHREAD_MUTEX_INITIALIZER;
+    long r = -1;
+    pthread_mutex_lock(&fmu);
+    if (grom_fasta_attach(&S->fa, S->fasta_name) == 0) r = grom_fasta_load(&S->fa, fi, buf, cap);
+    pthread_mutex_unlock(&fmu);
+    return r;
+}
+
 /* find_disc_svs loads each chromosome in order (GROM.c:21009-21045); here a
  * few threads do it ahead of the scans (one thread at ~0.9 GB/s of FASTA was
  * slower than the GPU decode: the whole run waited on it), each taking the
@@ -1211,7 +1311,17 @@ static void *fasta_main(void *arg) {
         if (stop) break;
         chrom_plan *c = F->plan[k];
         c->ref = ref_alloc(c->len);
-        if (c->ref && grom_fasta_load_at(&F->S->fa, c->fasta_idx, c->ref, c->len) < 0) {
+        if (c->ref && g_fdev) {
+            /* the device loader: the bytes stay in HBM for the stage and come back for the host's SV rows */
+            pthread_mutex_lock(&g_fdev_mu);
+            const int64_t r = grom_fasta_dev_load(g_fdev, c->fasta_idx, c->ref, c->len, &c->d_ref);
+            pthread_mutex_unlock(&g_fdev_mu);
+            if (r != c->len) {
+                if (r != GROM_FASTA_HOST_ONLY) fprintf(stderr, "grom: device FASTA loader: %s; reading %s on the host\n", grom_last_error(), c->name);
+                plan_release_dref(c);
+                cli_fasta_host_load(F->S, c->fasta_idx, c->ref, c->len);
+            }
+        } else if (c->ref && grom_fasta_load_at(&F->S->fa, c->fasta_idx, c->ref, c->len) < 0) {
             /* (the shared-stream loader: one thread at a time) */
             static pthread_mutex_t fmu = PTHREAD_MUTEX_INITIALIZER;
             pthread_mutex_lock(&fmu);
@@ -1490,6 +1600,7 @@ static int run_streamed(cli_state *S) {
     pthread_cond_init(&F.cv, NULL);
     /* GROM_FASTA_THREADS (default 3) */
     n_fthr = getenv("GROM_FASTA_THREADS") ? atoi(getenv("GROM_FASTA_THREADS")) : 3;
+    if (g_fdev) n_fthr = 1; /* the device loader: one thread feeds it */
     if (n_fthr < 1) n_fthr = 1;
     if (n_fthr > FASTA_THREADS_MAX) n_fthr = FASTA_THREADS_MAX;
     for (int t = 0; t < n_fthr; t++)
@@ -1526,7 +1637,10 @@ static int run_streamed(cli_state *S) {
             F.consumed = q + 1;
             pthread_cond_broadcast(&F.cv);
             pthread_mutex_unlock(&F.mu);
-            if (!plan[k]->ref || grom_stage_set_ref(st, plan[k]->ref, plan[k]->len) != GROM_OK) {
+            /* the device loader's bytes go stage-ward device-to-device (same GPU), else from the host copy */
+            const int d2d = plan[k]->ref && plan[k]->d_ref && dev_of[pidx[k]] == g_fdev_device;
+            if (!plan[k]->ref || (d2d ? grom_stage_set_ref_device(st, plan[k]->d_ref, plan[k]->len)
+                                      : grom_stage_set_ref(st, plan[k]->ref, plan[k]->len)) != GROM_OK) {
                 fprintf(stderr, "grom: staging the reference of %s failed: %s\n", plan[k]->name, grom_last_error());
                 status = 1;
                 pd_release_stage(pd, st);
@@ -1799,12 +1913,10 @@ static int cli_run(int argc, char **argv, int force_serial) {
         fclose(probe);
     }
     if (!S->fasta_name) { printf("ERROR: No reference file specified.\n"); goto out_hdr; }
-    if (grom_fasta_open_cached(&S->fa, S->fasta_name) != 0) {
-        printf("\nCould not open %s\n", S->fasta_name);
-        goto out_hdr;
-    }
     g_plan_only = getenv("GROM_PLAN_ONLY") != NULL;
-    if (!g_plan_only) S->hip_started = pthread_create(&S->hip_thr, NULL, hip_init_main, &S->device) == 0;
+    if (cli_fasta_open(S, force_serial) != 0) goto out_hdr;
+    if (!g_plan_only && !S->hip_started && !S->hip_done)
+        S->hip_started = pthread_create(&S->hip_thr, NULL, hip_init_main, &S->device) == 0;
     fp_sampler fps;
     memset(&fps, 0, sizeof(fps));
     if (!g_plan_only && S->verbose) fp_start(&fps, S->device);
@@ -1843,8 +1955,17 @@ static int cli_run(int argc, char **argv, int force_serial) {
     {
         long *lens = calloc(n_fi > 0 ? n_fi : 1, sizeof(long));
         const int thr = host_cpus() < 16 ? host_cpus() : 16;
+        if (g_fdev) {
+            /* the index pass measured them; a table adopted from .info: a length-only load each */
+            for (int a = 0; a < n_fi; a++) {
+                int64_t L = grom_fasta_dev_load(g_fdev, fi_list[a], NULL, 0, NULL);
+                if (L < 0) L = cli_fasta_host_load(S, fi_list[a], NULL, 0);
+                fi_len[fi_list[a]] = (long)L;
+            }
+        } else {
         const int ok = getenv("GROM_FASTA_SERIAL") == NULL && grom_fasta_lengths(&S->fa, fi_list, n_fi, lens, thr) == 0;
         for (int a = 0; a < n_fi; a++) fi_len[fi_list[a]] = ok ? lens[a] : grom_fasta_load(&S->fa, fi_list[a], NULL, 0);
+        }
         free(lens);
     }
     for (int t = 0; t < S->hdr.n_ref; t++) {
@@ -1886,6 +2007,14 @@ static int cli_run(int argc, char **argv, int force_serial) {
     const char *ser = getenv("GROM_SERIAL_DECODE");
     if (force_serial || (ser && atoi(ser) > 0)) ret = run_serial(S);
     else ret = run_streamed(S);
+    if (g_fdev && S->verbose) {
+        double ms[8];
+        grom_fasta_dev_times(g_fdev, ms);
+        fprintf(stderr, "grom: device FASTA loader (%s, device %d): file read + upload %.1f ms, inflate %.1f ms, index pass "
+                        "kernels %.1f ms, load kernels %.1f ms, copies to the host %.1f ms; wall: open %.1f ms, index %.1f ms, "
+                        "loads %.1f ms\n", grom_fasta_dev_is_bgzf(g_fdev) ? "BGZF" : "plain text", g_fdev_device, ms[0], ms[1],
+                ms[2], ms[3], ms[4], ms[5], ms[6], ms[7]);
+    }
     tables_join(S);
     for (int d = 0; d < S->n_init; d++) grom_dev_fini(d);
     if (S->verbose && S->t_outputs > 0)
@@ -1896,6 +2025,7 @@ static int cli_run(int argc, char **argv, int force_serial) {
     for (int i = 0; i < S->n_cand; i++) {
         free(S->plan[i].target);
         free(S->plan[i].ref);
+        plan_release_dref(&S->plan[i]);
     }
     free(S->plan);
     free(S->hez);
@@ -1904,6 +2034,13 @@ static int cli_run(int argc, char **argv, int force_serial) {
 out_hdr:
     tables_join(S);
     hip_ready(S);
+    if (g_fdev) {
+        pthread_mutex_lock(&g_fdev_mu);
+        grom_fasta_dev_close(g_fdev);
+        g_fdev = NULL;
+        g_fdev_device = -1;
+        pthread_mutex_unlock(&g_fdev_mu);
+    }
     dd_ctx_drop_prepared();
     bam_free_header(&S->hdr);
     free(S);

@@ -1385,6 +1385,22 @@ int grom_stage_set_ref(grom_stage *s, const char *ref, int64_t len) {
     return GROM_OK;
 }
 
+int grom_stage_set_ref_device(grom_stage *s, const void *d_ref, int64_t len) {
+    if (!s || (!d_ref && len > 0) || len < 0) { set_err("grom_stage_set_ref_device: bad argument"); return GROM_E_ARG; }
+    HIPCHK(hipSetDevice(s->device));
+    size_t need[SA_N], keep[SA_N];
+    stage_used(s, need);
+    stage_used(s, keep);
+    need[SA_REF] = (size_t)std::max<int64_t>(len, 16);
+    keep[SA_REF] = 0;
+    int rc = stage_reserve(s, need, keep);
+    if (rc) return rc;
+    // (the reference came from the device loader: no host-to-device bytes)
+    if (len > 0) HIPCHK(hipMemcpyAsync(s->a(SA_REF), d_ref, (size_t)len, hipMemcpyDeviceToDevice, s->st));
+    s->ref_len = len;
+    return GROM_OK;
+}
+
 static int stage_ticket_wait(grom_stage *s, int64_t t) {
     if (t < s->done_upto) return GROM_OK;
     HIPCHK(hipEventSynchronize(s->ev[t % GROM_STAGE_EVENTS]));

@@ -12,6 +12,9 @@
 
 /* ---------------- FASTA ---------------- */
 
+static void fasta_load_info(grom_fasta *f, const char *path, int *cap);
+static void fasta_save_info(const grom_fasta *f, const char *path);
+
 static int fasta_grow(grom_fasta *f, int want, int *cap) {
     if (want <= *cap) return 0;
     int c = *cap ? *cap : 64;
@@ -26,6 +29,105 @@ static int fasta_grow(grom_fasta *f, int want, int *cap) {
     *cap = c;
     return 0;
 }
+
+int grom_fasta_file_kind(const char *path) {
+    FILE *fp = fopen(path, "rb");
+    if (!fp) return -1;
+    unsigned char h[18];
+    const size_t k = fread(h, 1, sizeof(h), fp);
+    fclose(fp);
+    if (k < 2 || h[0] != 0x1f || h[1] != 0x8b) return 0;
+    if (k < 18 || h[2] != 8 || !(h[3] & 4)) return 2;
+    const int xlen = h[10] | (h[11] << 8);
+    /* the BC subfield comes first in every BGZF writer's block; one that is
+     * further back is found by the block table, this is the 18-byte probe */
+    if (xlen >= 6 && h[12] == 'B' && h[13] == 'C' && h[14] == 2 && h[15] == 0) return 1;
+    return 2;
+}
+
+/* a BGZF file inflated whole (bamio.c's reader: the host decoder) */
+static int fasta_inflate_host(const char *path, char **mem, long *len) {
+    bgzf_reader r;
+    if (bgzf_open_read(&r, path) != 0) return -1;
+    size_t cap = (size_t)1 << 20, n = 0;
+    char *b = malloc(cap);
+    int rc = b ? 0 : -1;
+    while (rc == 0) {
+        if (cap - n < 65536) {
+            char *nb = realloc(b, cap * 2);
+            if (!nb) { rc = -1; break; }
+            b = nb;
+            cap *= 2;
+        }
+        /* (bgzf_read wants every byte it is asked for: one byte opens the next
+         * block with data, then the rest of that block) */
+        int k = bgzf_read(&r, b + n, 1);
+        if (k < 0) rc = -1;
+        if (k <= 0) break;
+        n += 1;
+        const int rest = r.blk_len - r.blk_off;
+        if (rest > 0) {
+            k = bgzf_read(&r, b + n, rest);
+            if (k != rest) { rc = -1; break; }
+            n += (size_t)rest;
+        }
+    }
+    bgzf_close_read(&r);
+    if (rc != 0) { free(b); return -1; }
+    *mem = b;
+    *len = (long)n;
+    return 0;
+}
+
+int grom_fasta_attach(grom_fasta *f, const char *path) {
+    if (f->fh) return 0;
+    const int kind = grom_fasta_file_kind(path);
+    if (kind < 0) return -1;
+    if (kind == 2) {
+        char m[4400];
+        snprintf(m, sizeof(m), "%s is gzip-compressed but not BGZF: recompress it with bgzip (a single DEFLATE stream "
+                 "cannot be read in parallel)", path);
+        grom_set_last_error(m);
+        return -1;
+    }
+    if (kind == 0) {
+        f->fh = fopen(path, "r");
+        return f->fh ? 0 : -1;
+    }
+    if (fasta_inflate_host(path, &f->mem, &f->mem_len) != 0) {
+        char m[4400];
+        snprintf(m, sizeof(m), "%s: a BGZF block does not inflate", path);
+        grom_set_last_error(m);
+        return -1;
+    }
+    f->fh = f->mem_len > 0 ? fmemopen(f->mem, (size_t)f->mem_len, "r") : fopen("/dev/null", "r");
+    if (!f->fh) { free(f->mem); f->mem = NULL; f->mem_len = 0; return -1; }
+    return 0;
+}
+
+int grom_fasta_reserve(grom_fasta *f, int n) {
+    int cap = 0;
+    free(f->names); free(f->name_len); free(f->file_pos); free(f->len);
+    f->names = NULL; f->name_len = NULL; f->file_pos = NULL; f->len = NULL;
+    return fasta_grow(f, n > 0 ? n : 1, &cap);
+}
+
+int grom_fasta_header_name(const char *line, int L, char name[GROM_MAX_CHR_NAME_LEN]) {
+    int name_end = L;
+    for (int w = L - 1; w > 0; w--)
+        if (!isgraph((unsigned char)line[w])) name_end = w;
+    if (name_end >= GROM_MAX_CHR_NAME_LEN) name_end = GROM_MAX_CHR_NAME_LEN;
+    memset(name, 0, GROM_MAX_CHR_NAME_LEN);
+    for (int a = 1; a < name_end; a++) name[a - 1] = (char)tolower((unsigned char)line[a]);
+    return name_end - 1;
+}
+
+void grom_fasta_info_load(grom_fasta *f, const char *path) {
+    int cap = 0;
+    fasta_load_info(f, path, &cap);
+}
+
+void grom_fasta_info_save(const grom_fasta *f, const char *path) { fasta_save_info(f, path); }
 
 /* load_genome_info (GROM.c:1047-1081): "<n> <mappable>" then per chromosome
  * "<i> <name_len> <file_pos> <len> <name>"; a line that does not parse or is
@@ -73,8 +175,7 @@ static void fasta_save_info(const grom_fasta *f, const char *path) {
 
 int grom_fasta_open_cached(grom_fasta *f, const char *path) {
     memset(f, 0, sizeof(*f));
-    f->fh = fopen(path, "r");
-    if (!f->fh) return -1;
+    if (grom_fasta_attach(f, path) != 0) return -1;
     int cap = 0;
     fasta_load_info(f, path, &cap);
     if (f->n > 0) return 0;
@@ -82,6 +183,7 @@ int grom_fasta_open_cached(grom_fasta *f, const char *path) {
      * (find_genome_length adds to a mappable length a failed load kept) */
     const long kept = f->mappable;
     fclose(f->fh);
+    free(f->mem);
     free(f->names);
     free(f->name_len);
     free(f->file_pos);
@@ -94,8 +196,7 @@ int grom_fasta_open_cached(grom_fasta *f, const char *path) {
 
 int grom_fasta_open(grom_fasta *f, const char *path) {
     memset(f, 0, sizeof(*f));
-    f->fh = fopen(path, "r");
-    if (!f->fh) return -1;
+    if (grom_fasta_attach(f, path) != 0) return -1;
     int cap = 64;
     f->names = malloc(sizeof(*f->names) * cap);
     f->name_len = malloc(sizeof(int) * cap);
@@ -115,9 +216,6 @@ int grom_fasta_open(grom_fasta *f, const char *path) {
             continue;
         }
         long here = ftell(f->fh);
-        int L = (int)strlen(line), name_end = L;
-        for (int w = L - 1; w > 0; w--)
-            if (!isgraph((unsigned char)line[w])) name_end = w;
         if (f->n > 0) f->len[f->n - 1] = cur_len;
         cur_len = 0;
         if (f->n >= GROM_MAX_CHR_NAMES) { f->n++; continue; }
@@ -128,10 +226,7 @@ int grom_fasta_open(grom_fasta *f, const char *path) {
             f->file_pos = realloc(f->file_pos, sizeof(long) * cap);
             f->len = realloc(f->len, sizeof(long) * cap);
         }
-        if (name_end >= GROM_MAX_CHR_NAME_LEN) name_end = GROM_MAX_CHR_NAME_LEN;
-        memset(f->names[f->n], 0, GROM_MAX_CHR_NAME_LEN);
-        for (int a = 1; a < name_end; a++) f->names[f->n][a - 1] = (char)tolower((unsigned char)line[a]);
-        f->name_len[f->n] = name_end - 1;
+        f->name_len[f->n] = grom_fasta_header_name(line, (int)strlen(line), f->names[f->n]);
         f->file_pos[f->n] = here;
         f->len[f->n] = 0;
         f->n++;
@@ -143,6 +238,7 @@ int grom_fasta_open(grom_fasta *f, const char *path) {
 
 void grom_fasta_close(grom_fasta *f) {
     if (f->fh) fclose(f->fh);
+    free(f->mem);
     free(f->names);
     free(f->name_len);
     free(f->file_pos);
@@ -180,7 +276,7 @@ long grom_fasta_load_at(const grom_fasta *f, int i, char *buf, long cap) {
     enum { BLK = 1 << 22 };
     char *b = malloc((size_t)BLK + 1024);
     if (!b) return -1;
-    const int fd = fileno(f->fh);
+    const int fd = f->mem ? -1 : fileno(f->fh);
     off_t off = (off_t)f->file_pos[i];
     size_t have = 0, p = 0;
     int eof = 0, prev_l = -1, alpha = 0;
@@ -190,7 +286,13 @@ long grom_fasta_load_at(const grom_fasta *f, int i, char *buf, long cap) {
             memmove(b, b + p, have - p);
             have -= p;
             p = 0;
-            const ssize_t k = pread(fd, b + have, BLK, off);
+            ssize_t k;
+            if (f->mem) { /* the inflated text of a BGZF file */
+                k = off < (off_t)f->mem_len ? (ssize_t)(f->mem_len - (long)off < BLK ? f->mem_len - (long)off : BLK) : 0;
+                if (k > 0) memcpy(b + have, f->mem + off, (size_t)k);
+            } else {
+                k = pread(fd, b + have, BLK, off);
+            }
             if (k < 0) { free(b); return -1; }
             if (k == 0) eof = 1;
             if (k > 0 && memchr(b + have, 0, (size_t)k)) { free(b); return -2; }
@@ -266,6 +368,32 @@ int grom_fasta_lengths(const grom_fasta *f, const int *idx, int n, long *out, in
     for (int t = 0; t < started; t++) pthread_join(th[t], NULL);
     pthread_mutex_destroy(&j.mu);
     return j.bad ? -1 : 0;
+}
+
+/* the host code by path (include/grom_amd.h): tests compare the device loader with these */
+int grom_fasta_host_index(const char *path, int cap, int64_t *mappable, char *names, int *name_len, int64_t *file_pos,
+                          int64_t *len) {
+    grom_fasta f;
+    if (!path || grom_fasta_open(&f, path) != 0) return GROM_E_ARG;
+    const int n = f.n;
+    if (mappable) *mappable = f.mappable;
+    for (int i = 0; i < n && i < cap; i++) {
+        if (names) memcpy(names + (size_t)i * GROM_MAX_CHR_NAME_LEN, f.names[i], GROM_MAX_CHR_NAME_LEN);
+        if (name_len) name_len[i] = f.name_len[i];
+        if (file_pos) file_pos[i] = f.file_pos[i];
+        if (len) len[i] = f.len[i];
+    }
+    grom_fasta_close(&f);
+    return n;
+}
+
+int64_t grom_fasta_host_load(const char *path, int i, char *buf, int64_t cap) {
+    grom_fasta f;
+    if (!path || grom_fasta_open(&f, path) != 0) return GROM_E_ARG;
+    int64_t r = GROM_E_ARG;
+    if (i >= 0 && i < f.n) r = grom_fasta_load(&f, i, buf, (long)cap);
+    grom_fasta_close(&f);
+    return r;
 }
 
 int grom_target_name_lc(const char *target, char *out, int cap) {

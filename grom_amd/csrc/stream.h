@@ -36,8 +36,28 @@ typedef struct grom_fasta {
     long mappable;         /* g_mappable_genome_length */
     int loader_line_len;   /* state carried across loads (GROM.c:21014-21029) */
     int loader_alpha_len;
+    char *mem;             /* a BGZF file's inflated text (fh reads it), else NULL */
+    long mem_len;
 } grom_fasta;
 
+/* what a -r file holds: 0 plain text, 1 BGZF, 2 gzip that is not BGZF (refused:
+ * one DEFLATE stream cannot be inflated block-parallel), -1 it does not open */
+int grom_fasta_file_kind(const char *path);
+/* the index's name rule on one header chunk (line[0] == '>', L bytes, no NUL):
+ * bytes 1.. to the first non-graph byte, lower-cased, at most
+ * GROM_MAX_CHR_NAME_LEN - 1 of them; returns name_len */
+int grom_fasta_header_name(const char *line, int L, char name[GROM_MAX_CHR_NAME_LEN]);
+/* the <fasta>.info cache alone (no stream is opened): load leaves n = 0 when
+ * the file is missing or does not parse */
+void grom_fasta_info_load(grom_fasta *f, const char *path);
+void grom_fasta_info_save(const grom_fasta *f, const char *path);
+/* a table that holds n entries (grom_fasta_info_load's and the device index's) */
+int grom_fasta_reserve(grom_fasta *f, int n);
+/* open the stream of a table-only grom_fasta (a BGZF file is inflated on the
+ * host and read through fmemopen); 0, -1 */
+int grom_fasta_attach(grom_fasta *f, const char *path);
+
+/* plain text, or BGZF inflated on the host */
 int grom_fasta_open(grom_fasta *f, const char *path); /* find_genome_length */
 /* the CLI's open: the <fasta>.info cache when it loads (load_genome_info),
  * else grom_fasta_open + save_genome_info (GROM.c:22308-22311) */

@@ -487,6 +487,55 @@ int grom_bai_summary(const char *bai_path, int64_t out[5]);
  * negative on error.  *visited gets the records the fetches returned. */
 int64_t grom_bai_selftest(const char *bam_path, int64_t n_queries, uint64_t seed, int64_t *visited);
 
+/* ---- the reference FASTA read on the device (fastadev.hip):
+ * plain text or BGZF (bgzip); the index (find_genome_length, GROM.c:1321-1428)
+ * and the loader (GROM.c:21009-21045) give the host code's results bit for
+ * bit.  One handle is used by one thread at a time. ---- */
+typedef struct grom_fasta_dev grom_fasta_dev;
+#define GROM_FASTA_NAME_LEN 50 /* max_chr_name_len, GROM.c:638 (names are NUL-padded) */
+/* "host only": the text holds a NUL byte (the host's fgets/strlen cut there)
+ * or more headers than the host table keeps; take the host path */
+#define GROM_FASTA_HOST_ONLY (-100)
+/* the file's bytes brought to `device` (BGZF blocks inflated there).  0 or a
+ * negative GROM_E_* code: GROM_E_NODEV no such device, GROM_E_ARG a file that
+ * does not open, a gzip file that is not BGZF (the message says to recompress
+ * with bgzip), a block that does not inflate.  GROM_FASTA_PIECE_KB sets the
+ * bytes per upload, inflate launch and scan piece (default 262144 = 256 MB). */
+int grom_fasta_dev_open(const char *path, int device, grom_fasta_dev **out);
+void grom_fasta_dev_close(grom_fasta_dev *d);
+/* 1 when the file is BGZF, 0 plain text */
+int grom_fasta_dev_is_bgzf(const grom_fasta_dev *d);
+/* the index pass: every entry's name, file_pos (an offset in the inflated
+ * text), len and the loader's length.  0, GROM_FASTA_HOST_ONLY or negative */
+int grom_fasta_dev_index(grom_fasta_dev *d, int *n, int64_t *mappable);
+/* entry i of the table (after grom_fasta_dev_index or _set_index; load_len is
+ * -1 until a load or the index pass measured it) */
+int grom_fasta_dev_entry(const grom_fasta_dev *d, int i, char name[GROM_FASTA_NAME_LEN], int *name_len,
+                         int64_t *file_pos, int64_t *len, int64_t *load_len);
+/* adopt a table read from <fasta>.info instead of the index pass (names: n
+ * rows of GROM_FASTA_NAME_LEN bytes) */
+int grom_fasta_dev_set_index(grom_fasta_dev *d, int n, int64_t mappable, const char *names, const int *name_len,
+                             const int64_t *file_pos, const int64_t *len);
+/* entry i loaded: returns the loader's length; with cap == 0 the length only.
+ * Else cap >= that length, the bytes are copied to host_buf (may be NULL) and
+ * stay in device memory at *dev_ptr (may be NULL: not kept) until
+ * grom_fasta_dev_release.  GROM_FASTA_HOST_ONLY, or a negative GROM_E_* code */
+int64_t grom_fasta_dev_load(grom_fasta_dev *d, int i, char *host_buf, int64_t cap, const void **dev_ptr);
+void grom_fasta_dev_release(grom_fasta_dev *d, const void *dev_ptr);
+/* ms = {file read + upload wall, inflate (HIP events), index pass kernels,
+ * load kernels, load device-to-host copies (wall), open wall, index wall, loads wall} */
+void grom_fasta_dev_times(const grom_fasta_dev *d, double ms[8]);
+/* the host code by path (grom_fasta_open / grom_fasta_load; BGZF inflated on
+ * the host): up to cap entries filled, returns the number of entries or
+ * negative; load returns the loader's length (bytes copied when it fits cap) */
+int grom_fasta_host_index(const char *path, int cap, int64_t *mappable, char *names, int *name_len, int64_t *file_pos,
+                          int64_t *len);
+int64_t grom_fasta_host_load(const char *path, int i, char *buf, int64_t cap);
+/* the bytes of a device reference (grom_fasta_dev_load's *dev_ptr, on the
+ * stage's device) copied device-to-device on the stage's stream; the source
+ * may be released once the stage's scan has run */
+int grom_stage_set_ref_device(grom_stage *s, const void *d_ref, int64_t len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,10 @@
  *                        raw CTX rows
  *   inflate <bam>        the device BGZF inflater's host twin against zlib on
  *                        every block (inflate_host.cpp)
+ *   fasta <fa|fa.gz>     the FASTA host code: BGZF detection, the host inflate
+ *                        and the index and loader over the inflated memory
+ *                        (stream.c), every entry loaded into an exact-fit
+ *                        buffer and into one a byte short
  *   svrows <rec>...      svcall.cpp's candidate lists, SV assembly and rows on
  *                        recorded GPU-scan inputs (GROM_SV_HITS_DUMP), every
  *                        record on its own thread, four rounds, outputs
@@ -103,6 +107,41 @@ static int cmd_inflate(const char *bam) {
     return bad != 0;
 }
 
+/* stream.h's FASTA front end, declared here as the library exports it */
+int grom_fasta_file_kind(const char *path);
+
+static int cmd_fasta(const char *path) {
+    const int kind = grom_fasta_file_kind(path);
+    int64_t mappable = 0;
+    const int n = grom_fasta_host_index(path, 0, &mappable, NULL, NULL, NULL, NULL);
+    if (n < 0) {
+        printf("fasta: kind %d, refused: %s\n", kind, grom_last_error());
+        return kind == 2 ? 0 : 1;
+    }
+    char *names = calloc((size_t)(n > 0 ? n : 1), GROM_FASTA_NAME_LEN);
+    int *nl = calloc((size_t)(n > 0 ? n : 1), sizeof(int));
+    int64_t *fp = calloc((size_t)(n > 0 ? n : 1), sizeof(int64_t)), *ln = calloc((size_t)(n > 0 ? n : 1), sizeof(int64_t));
+    grom_fasta_host_index(path, n, &mappable, names, nl, fp, ln);
+    int64_t total = 0;
+    int bad = 0;
+    for (int i = 0; i < n; i++) {
+        const int64_t L = grom_fasta_host_load(path, i, NULL, 0);
+        if (L < 0) { bad++; continue; }
+        char *a = malloc((size_t)L + 1), *b = malloc((size_t)L + 1);
+        /* an exact-fit buffer, and one byte short (nothing may be written) */
+        if (grom_fasta_host_load(path, i, a, L) != L) bad++;
+        memset(b, 0x5a, (size_t)L + 1);
+        if (L > 0 && (grom_fasta_host_load(path, i, b, L - 1) != L)) bad++;
+        total += L;
+        free(a);
+        free(b);
+    }
+    printf("fasta: kind %d, %d entries, mappable %lld, %lld bytes loaded, %d bad\n", kind, n, (long long)mappable,
+           (long long)total, bad);
+    free(names); free(nl); free(fp); free(ln);
+    return bad != 0;
+}
+
 typedef struct {
     const char *path;
     int rc;
@@ -134,7 +173,7 @@ static int cmd_svrows(int n, char **paths) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: san_driver cli|bai|fmt|synth|ctx|svrows|inflate ...\n");
+        fprintf(stderr, "usage: san_driver cli|bai|fmt|synth|ctx|svrows|inflate|fasta ...\n");
         return 2;
     }
     if (!strcmp(argv[1], "cli")) return grom_cli_main(argc - 1, argv + 1);
@@ -144,6 +183,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "ctx")) return cmd_ctx();
     if (!strcmp(argv[1], "svrows") && argc >= 3) return cmd_svrows(argc - 2, argv + 2);
     if (!strcmp(argv[1], "inflate") && argc >= 3) return cmd_inflate(argv[2]);
+    if (!strcmp(argv[1], "fasta") && argc >= 3) return cmd_fasta(argv[2]);
     fprintf(stderr, "bad arguments\n");
     return 2;
 }
