@@ -12,7 +12,7 @@ BINDIR  = grom_amd/bin
 HOST_SRC = grom_amd/csrc/bamio.c grom_amd/csrc/stream.c grom_amd/csrc/tables.c grom_amd/csrc/synth.c grom_amd/csrc/hostapi.c grom_amd/csrc/grom_main.c grom_amd/csrc/pdecode.c
 HOST_OBJ = $(patsubst grom_amd/csrc/%.c,build/%.o,$(HOST_SRC)) build/snvfmt.o build/svcall.o build/inflate_host.o build/devmem.o
 DEV_OBJ = build/scan.o build/cnv.o build/sv.o build/ddecode.o build/baidev.o build/fastadev.o
-HDRS = include/grom_amd.h grom_amd/csrc/devmem.h grom_amd/csrc/scan_common.h grom_amd/csrc/bamio.h grom_amd/csrc/stream.h grom_amd/csrc/synth.h grom_amd/csrc/pdecode.h grom_amd/csrc/ddecode.h
+HDRS = include/grom_amd.h grom_amd/csrc/devmem.h grom_amd/csrc/devbuf.h grom_amd/csrc/scan_common.h grom_amd/csrc/bamio.h grom_amd/csrc/stream.h grom_amd/csrc/synth.h grom_amd/csrc/pdecode.h grom_amd/csrc/ddecode.h
 KHDRS = grom_amd/csrc/k_scan_tile.h grom_amd/csrc/device_common.h grom_amd/csrc/snvfmt.h
 
 all: $(LIBDIR)/libgrom_amd.so $(BINDIR)/grom $(BINDIR)/grom_synth $(BINDIR)/gromc_binding oracle
@@ -148,6 +148,12 @@ $(SANDIR)/san_driver: tools/san_driver.c $(SAN_OBJ) $(SANDIR)/svcall.o $(SANDIR)
 $(SANDIR)/grom_synth: tools/grom_synth.c $(SANDIR)/synth.o $(SANDIR)/bamio.o
 	$(CC) -O1 -g -fno-omit-frame-pointer $(SANFLAGS) -o $@ $^ -lz -lm -ldl -lpthread
 
-sanitize: $(SANDIR)/san_driver $(SANDIR)/grom_synth
+# the growable device buffer (devbuf.h) over malloc-backed stand-ins for the
+# allocator: no HIP, no device (tests/test_devbuf.py)
+$(SANDIR)/devbuf_check: tools/devbuf_check.cpp grom_amd/csrc/devbuf.h grom_amd/csrc/devmem.h
+	@mkdir -p $(SANDIR)
+	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -std=c++17 $(SANFLAGS) $< -o $@
+
+sanitize: $(SANDIR)/san_driver $(SANDIR)/grom_synth $(SANDIR)/devbuf_check
 
 .PHONY: sanitize

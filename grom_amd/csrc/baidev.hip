@@ -1,9 +1,10 @@
 // baidev.hip -- a missing BAM index built on the device.
 //
 // The host builder (bai_build, bamio.c) inflates and walks every record of the
-// file on one thread.  Here the file is read once and goes through the device
-// in pieces of whole BGZF blocks: the blocks are inflated by the decoder's
-// inflater (dd_inflate_launch, ddecode.hip) from the decoder's compressed
+// file on one thread.  Here the file is read once (DdBgzfFile, ddecode.h: whole
+// blocks through two pinned ring buffers) and goes through the device in
+// pieces of whole BGZF blocks: the blocks are inflated by the decoder's
+// inflater (dd_inflate_launch, ddecode.h) from the decoder's compressed
 // slots (dd_comp_*), an index-free walk finds the record starts, one lane per
 // record takes the facts an index needs (target id, begin, end, bin, the
 // record's virtual offsets) and reductions turn them into the runs of records
@@ -27,6 +28,9 @@
 // taken is the true chain's: a wrong guess costs time and never changes the
 // result.  Candidates are arbitrary bytes: every load is bounded by the
 // piece's length, and a chain that leaves the record limits is reported.
+//
+// The builder's device buffers are DevBufs (devbuf.h) accounted as decode
+// memory: they grow to the largest piece and free themselves with the builder.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,12 +47,7 @@
 #include "../../include/grom_amd.h"
 #include "bamio.h"
 #include "ddecode.h"
-#include "devmem.h"
-
-extern "C" size_t dd_inflate_tok_bytes(int64_t n_blk);
-extern "C" int dd_inflate_launch(hipStream_t st, const uint8_t *d_comp, int64_t comp_cap, const DdBlock *d_blk,
-                                 int64_t n_blk, uint8_t *d_out, int64_t out_base, int64_t out_cap, uint8_t *d_status,
-                                 uint32_t *d_bad, uint32_t *d_bounds, uint32_t *d_tok, size_t tok_bytes);
+#include "devbuf.h"
 
 namespace {
 
@@ -442,23 +441,7 @@ __global__ void k_ix_runs(int64_t R, const int32_t *__restrict__ tid, const uint
     }
 }
 
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
-template <class T> T *P(Buf &b) { return (T *)b.p; }
-
-int bgrow(Buf &b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.cap >= bytes) return 0;
-    if (b.p) grom_dev_free(b.p, b.cap, GROM_DEVCAT_DECODE);
-    b.p = nullptr;
-    b.cap = 0;
-    const size_t want = bytes + bytes / 8 + 256;
-    if (grom_dev_malloc(&b.p, want, GROM_DEVCAT_DECODE) != 0) return -1;
-    b.cap = want;
-    return 0;
-}
+using Buf = DevBufOf<GROM_DEVCAT_DECODE, 256>;  // decode memory, an eighth of slack (devbuf.h)
 
 // the BAM header through the host reader: its length in the inflated stream
 // (the first record's position) and the references' lengths
@@ -503,7 +486,7 @@ struct HostBlk {
     uint32_t len;
 };
 
-// one piece as read from the file: whole blocks from file offset c0 on
+// one piece as read from the file (DdBgzfFile): whole blocks from file offset c0 on
 struct PieceIn {
     std::vector<DdBlock> blk;  // in_off in the piece's compressed bytes, out_off from 0
     int64_t nblk = 0, comp_len = 0, ubytes = 0, c0 = 0;
@@ -513,17 +496,14 @@ struct PieceIn {
 struct IxBuild {
     int device = 0, guess = 1;
     int64_t piece_bytes = (int64_t)3 << 30, comp_read = (int64_t)256 << 20;
-    FILE *fp = nullptr;
-    int64_t file_size = 0, foff = 0;
+    DdBgzfFile in;  // the BAM, read in whole blocks through two pinned ring buffers
     std::vector<int32_t> ref_len;
     int32_t n_ref = 0;
     dd_ctx *ctx = nullptr;
     hipStream_t st = nullptr;
     hipEvent_t ev[5] = {};
-    uint8_t *ring[2] = {nullptr, nullptr};
     int64_t *h_small = nullptr;  // pinned: the misc words (16 x 8 bytes), then two scalars
     PieceIn pin[2];
-    std::vector<DdBlock> tab_all;
     Buf U[2], dblk, status, tok, misc, sub_st, sub_n, sub_base, cg, cex, tmp, tu, tc, off, tid, pos, end, binu, vbeg,
         vend, key, pre, runs, lin, lin_base;
     std::vector<HostBlk> keep;
@@ -539,20 +519,16 @@ struct IxBuild {
     double ms_inflate = 0, ms_walk = 0, ms_reduce = 0;
     char err[512] = {0};
 
+    explicit IxBuild(const char *bam_path) : in(bam_path) {}
+    // the stream is drained and the decode context (whose copy stream reads
+    // the ring buffers) freed here; the buffers and `in` free themselves after
     ~IxBuild() {
         if (st) (void)hipStreamSynchronize(st);
         if (ctx) dd_ctx_free(ctx);
-        Buf *all[] = {&U[0], &U[1], &dblk, &status, &tok, &misc, &sub_st, &sub_n, &sub_base, &cg, &cex, &tmp, &tu, &tc,
-                      &off, &tid, &pos, &end, &binu, &vbeg, &vend, &key, &pre, &runs, &lin, &lin_base};
-        for (Buf *b : all)
-            if (b->p) grom_dev_free(b->p, b->cap, GROM_DEVCAT_DECODE);
         for (int k = 0; k < 5; k++)
             if (ev[k]) (void)hipEventDestroy(ev[k]);
-        for (int k = 0; k < 2; k++)
-            if (ring[k]) (void)hipHostFree(ring[k]);
         if (h_small) (void)hipHostFree(h_small);
         if (st) (void)hipStreamDestroy(st);
-        if (fp) fclose(fp);
         for (bai_racc *a : racc) bai_racc_free(a);
     }
 
@@ -569,10 +545,9 @@ struct IxBuild {
             return GROM_E_HIP;                                                                                    \
         }                                                                                                         \
     } while (0)
-#define IXG(b, bytes)                                                                                   \
-    do {                                                                                                \
-        if (bgrow((b), (bytes))) return fail(GROM_E_NOMEM, "device index build: hipMalloc(%lld) failed", \
-                                             (long long)(bytes));                                       \
+#define IXG(b, bytes)                                                                                                 \
+    do {                                                                                                              \
+        if ((b).grow(bytes)) return fail(GROM_E_NOMEM, "device index build: hipMalloc(%lld) failed", (long long)(bytes)); \
     } while (0)
 
     // the next piece's blocks read into ring buffer s and sent to compressed slot s
@@ -580,30 +555,19 @@ struct IxBuild {
         PieceIn &p = pin[s];
         p.nblk = 0;
         p.comp_len = p.ubytes = 0;
-        p.c0 = foff;
+        p.c0 = in.off;
         p.last = false;
         p.blk.clear();
-        if (foff >= file_size) return 0;
+        if (in.off >= in.size) return 0;
         if (dd_comp_ring_wait(ctx, s) != 0) return fail(GROM_E_HIP, "device index build: the copy ring failed");
-        const int64_t want = std::min<int64_t>(comp_read, file_size - foff);
-        if (fseeko(fp, (off_t)foff, SEEK_SET) != 0 || (int64_t)fread(ring[s], 1, (size_t)want, fp) != want)
-            return fail(GROM_E_ARG, "device index build: read error at byte %lld", (long long)foff);
-        memset(ring[s] + want, 0, 64);
-        int64_t ob = 0, used = 0;
-        const int64_t n = dd_block_table_prefix(ring[s], want, tab_all.data(), (int64_t)tab_all.size(), &ob, &used);
-        if (n <= 0) return fail(GROM_E_ARG, "device index build: no whole BGZF block at byte %lld", (long long)foff);
-        const int64_t have = std::min<int64_t>(n, (int64_t)tab_all.size());
-        int64_t nb = 0, ub = 0;
-        while (nb < have && (nb == 0 || ub + tab_all[(size_t)nb].out_len <= piece_bytes)) ub += tab_all[(size_t)nb++].out_len;
-        p.blk.assign(tab_all.begin(), tab_all.begin() + nb);
+        const int64_t nb = in.read(s, piece_bytes, &p.comp_len, &p.ubytes);
+        if (nb == DD_READ_IO) return fail(GROM_E_ARG, "device index build: read error at byte %lld", (long long)in.off);
+        if (nb <= 0) return fail(GROM_E_ARG, "device index build: no whole BGZF block at byte %lld", (long long)in.off);
+        p.blk.assign(in.tab.begin(), in.tab.begin() + nb);
         p.nblk = nb;
-        p.ubytes = ub;
-        const DdBlock &lb = p.blk[(size_t)nb - 1];
-        p.comp_len = lb.in_off + (int64_t)lb.in_len + 8;
-        foff += p.comp_len;
-        p.last = foff >= file_size;
+        p.last = in.off >= in.size;
         if (dd_comp_begin(ctx, s, p.comp_len, err, sizeof(err)) != 0 ||
-            dd_comp_chunk(ctx, s, s, ring[s], 0, p.comp_len, err, sizeof(err)) != 0 ||
+            dd_comp_chunk(ctx, s, s, in.ring[s], 0, p.comp_len, err, sizeof(err)) != 0 ||
             dd_comp_end(ctx, s, p.comp_len, err, sizeof(err)) != 0)
             return GROM_E_HIP;
         return 0;
@@ -641,14 +605,13 @@ struct IxBuild {
         if (e && atof(e) > 0) piece_bytes = std::max<int64_t>((int64_t)(atof(e) * 1024.0), 4096);
         if (getenv("GROM_INDEX_GUESS")) guess = atoi(getenv("GROM_INDEX_GUESS"));
         comp_read = std::min<int64_t>(comp_read, std::max<int64_t>(piece_bytes, 65536) + 65536);
-        comp_read = std::min<int64_t>(comp_read, file_size);
+        comp_read = std::min<int64_t>(comp_read, in.size);
         comp_read = std::max<int64_t>(comp_read, 4096);
-        tab_all.resize((size_t)(comp_read / 512 + 64));
         ctx = dd_ctx_new(device);
         if (!ctx) return fail(GROM_E_HIP, "device index build: no decode context on device %lld", device);
         IXK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         for (int k = 0; k < 5; k++) IXK(hipEventCreate(&ev[k]));
-        for (int k = 0; k < 2; k++) IXK(hipHostMalloc((void **)&ring[k], (size_t)comp_read + 64, 0));
+        IXK((hipError_t)in.rings(comp_read, (size_t)(comp_read / 512 + 64)));
         IXK(hipHostMalloc((void **)&h_small, 32 * sizeof(int64_t), 0));
         IXG(misc, IX_MISC_BYTES);
         IXK(hipMemsetAsync(misc.p, 0, IX_MISC_BYTES, st));
@@ -698,7 +661,7 @@ struct IxBuild {
             const int s = (int)(k & 1);
             PieceIn &p = pin[s];
             if (p.nblk == 0) {
-                if (foff < file_size) return fail(GROM_E_ARG, "device index build: no whole BGZF block at byte %lld", foff);
+                if (in.off < in.size) return fail(GROM_E_ARG, "device index build: no whole BGZF block at byte %lld", in.off);
                 if (carry_len != 0 || start > 0) return fail(GROM_E_ARG, "device index build: the BAM ends inside a record");
                 break;
             }
@@ -902,19 +865,16 @@ extern "C" int grom_bai_build_device(const char *bam_path, const char *bai_path,
     const std::string tmp = bai + ".tmp." + std::to_string((long long)getpid());
     int rc;
     {
-        IxBuild B;
+        IxBuild B(bam_path);
         B.device = device;
         int64_t hdr_len = 0;
-        B.fp = fopen(bam_path, "rb");
-        if (!B.fp || ix_read_header(bam_path, &hdr_len, B.ref_len) != 0) {
+        if (!B.in.fp || ix_read_header(bam_path, &hdr_len, B.ref_len) != 0) {
             char m[4400];
             snprintf(m, sizeof(m), "grom_bai_build_device: cannot read the BAM header of %s", bam_path);
             grom_set_last_error(m);
             return GROM_E_ARG;
         }
         B.n_ref = (int32_t)B.ref_len.size();
-        fseeko(B.fp, 0, SEEK_END);
-        B.file_size = (int64_t)ftello(B.fp);
         rc = B.run(hdr_len);
         if (rc == 0) rc = B.write(tmp.c_str());
         if (rc == 0 && rename(tmp.c_str(), bai.c_str()) != 0) rc = B.fail(GROM_E_ARG, "device index build: cannot rename the index file");

@@ -53,6 +53,7 @@
 
 #include "cnv.h"
 #include "ddecode.h"
+#include "devbuf.h"
 #include "copystats.h"  // (GROM_COPY_STATS, last: it wraps the runtime copy calls)
 
 namespace {
@@ -3178,12 +3179,7 @@ __global__ void k_cnv_calls_valid(const CallRec *calls, uint32_t n, const uint8_
 }
 
 // ---------------- host side ----------------
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-    bool own = false;          // p is this buffer's own allocation (else a piece of `ar`'s phase)
-    grom_arena *ar = nullptr;  // the context's phase arena (cnv_scratch_phase), or none
-};
+using Buf = DevBufOf<GROM_DEVCAT_CNV, 256>;  // (its arena: the context's phase arena, cnv_scratch_phase)
 
 }  // namespace
 
@@ -3232,23 +3228,10 @@ namespace {
     } while (0)
 
 static int grow(Buf &b, size_t bytes, char *err, size_t errlen) {
-    if (bytes == 0) bytes = 16;
-    if (b.cap >= bytes) return GROM_OK;
-    if (b.p && b.own) grom_dev_free(b.p, b.cap, GROM_DEVCAT_CNV);
-    b.p = nullptr;
-    b.cap = 0;
-    b.own = false;
-    size_t want = bytes + bytes / 8 + 256;
-    if (b.ar && (b.p = grom_arena_take(b.ar, want)) != nullptr) {
-        b.cap = want;
-        return GROM_OK;
-    }
-    if (grom_dev_malloc(&b.p, want, GROM_DEVCAT_CNV)) {
-        snprintf(err, errlen, "hipMalloc(%zu) failed in the CNV path", want);
+    if (b.grow(bytes)) {
+        snprintf(err, errlen, "hipMalloc(%zu) failed in the CNV path", b.want(bytes));
         return GROM_E_NOMEM;
     }
-    b.cap = want;
-    b.own = true;
     return GROM_OK;
 }
 
@@ -3525,20 +3508,11 @@ int cnv_prelaunch(CnvScratch *S, hipStream_t after, const grom_params &P, const 
 // a new CNV phase (scan.hip): with an arena every buffer but the GC windows
 // (written beside the pileup by cnv_prelaunch) is carved from it
 void cnv_scratch_phase(CnvScratch *S, grom_arena *ar) {
-    auto reset = [ar](Buf *b) {
-        if (b->own && ar) grom_dev_free(b->p, b->cap, GROM_DEVCAT_CNV);  // (an overflow of the last phase)
-        if (!b->own || ar) {
-            b->p = nullptr;
-            b->cap = 0;
-            b->own = false;
-        }
-        b->ar = ar;
-    };
     Buf *all[] = CNV_PHASE_BUFS(S);
-    for (Buf *b : all) reset(b);
+    for (Buf *b : all) b->rebind(ar);
     for (KindBufs &K : S->kb) {
         Buf *kall[] = CNV_KIND_BUFS(K);
-        for (Buf *b : kall) reset(b);
+        for (Buf *b : kall) b->rebind(ar);
     }
 }
 
@@ -3550,22 +3524,13 @@ void cnv_scratch_sync(CnvScratch *S) {
 
 void cnv_scratch_free(CnvScratch *S) {
     if (!S) return;
+    cnv_scratch_sync(S);  // the buffers free themselves at the delete below, after their streams are gone
     if (S->h_cn) (void)hipHostFree(S->h_cn);
     S->h_cn = nullptr;
     for (auto &b : S->pin)
         if (b.p) (void)hipHostFree(b.p);
-    Buf *all[] = CNV_PHASE_BUFS(S);
-    for (Buf *b : all)
-        if (b->p && b->own) grom_dev_free(b->p, b->cap, GROM_DEVCAT_CNV);
-    Buf *gc[] = {&S->gcw, &S->acw, &S->rtype};
-    for (Buf *b : gc)
-        if (b->p && b->own) grom_dev_free(b->p, b->cap, GROM_DEVCAT_CNV);
-    for (KindBufs &K : S->kb) {
-        Buf *kall[] = CNV_KIND_BUFS(K);
-        for (Buf *b : kall)
-            if (b->p && b->own) grom_dev_free(b->p, b->cap, GROM_DEVCAT_CNV);
+    for (KindBufs &K : S->kb)
         if (K.st) (void)hipStreamDestroy(K.st);
-    }
     if (S->walk_in) (void)hipEventDestroy(S->walk_in);
     if (S->gc_done) (void)hipEventDestroy(S->gc_done);
     if (S->e0) (void)hipEventDestroy(S->e0);

@@ -6,6 +6,9 @@
 #define GROM_AMD_DDECODE_H
 
 #include <stdint.h>
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h> /* hipStream_t, for dd_inflate_launch */
+#endif
 
 #include "../../include/grom_amd.h"
 #include "devmem.h"
@@ -31,6 +34,20 @@ int64_t dd_block_table(const uint8_t *buf, int64_t len, DdBlock *out, int64_t ca
  * the buffer ends the table): their number, *consumed their bytes */
 int64_t dd_block_table_prefix(const uint8_t *buf, int64_t len, DdBlock *out, int64_t cap, int64_t *out_bytes,
                               int64_t *consumed);
+
+/* The inflater.  dd_inflate_tok_bytes: bytes of the token buffer the two-phase
+ * inflate of n_blk blocks needs (0: the one-phase inflate, no buffer).
+ * dd_inflate_launch: blocks d_blk[0..n_blk) of d_comp[0..comp_cap) inflated on
+ * `st` into d_out + (out_off - out_base), one GI_* code per block in d_status,
+ * the blocks that failed counted in *d_bad, bit 0 of *d_bounds set when a block
+ * lies outside comp_cap / out_cap (such a block is not touched); 0, or -1 when
+ * a launch failed */
+size_t dd_inflate_tok_bytes(int64_t n_blk);
+#ifdef __HIPCC__
+int dd_inflate_launch(hipStream_t st, const uint8_t *d_comp, int64_t comp_cap, const DdBlock *d_blk, int64_t n_blk,
+                      uint8_t *d_out, int64_t out_base, int64_t out_cap, uint8_t *d_status, uint32_t *d_bad,
+                      uint32_t *d_bounds, uint32_t *d_tok, size_t tok_bytes);
+#endif
 
 /* test hook: every whole block in the first max_bytes (<= 0: all) of a BAM
  * inflated on `device` and (check != 0) compared with zlib: the number of
@@ -155,5 +172,37 @@ int grom_copy_d2h(void *dst, const void *src, size_t n, int device);
 
 #ifdef __cplusplus
 }
+
+#include <stdio.h>
+
+#include <vector>
+
+/* A BGZF file read in whole blocks through two pinned ring buffers (the index
+ * builder, baidev.hip; the FASTA reader, fastadev.hip).  The caller sends the
+ * bytes of ring[s] where it wants them and waits for that copy before it reads
+ * into ring[s] again; it words the error messages. */
+struct DdBgzfFile {
+    FILE *fp = nullptr;                    /* NULL: the file did not open */
+    int64_t size = 0, off = 0;             /* the file's bytes; where the next read starts */
+    int64_t ring_bytes = 0;                /* bytes one read takes at most */
+    uint8_t *ring[2] = {nullptr, nullptr}; /* pinned, ring_bytes + 64 each */
+    std::vector<DdBlock> tab;              /* the blocks of the last read */
+
+    explicit DdBgzfFile(const char *path); /* opened and measured, positioned at byte 0 */
+    ~DdBgzfFile();
+    DdBgzfFile(const DdBgzfFile &) = delete;
+    DdBgzfFile &operator=(const DdBgzfFile &) = delete;
+    /* the ring buffers and a table of tab_cap blocks (one read yields at most
+     * that many); 0 or the hipError_t */
+    int rings(int64_t ring_bytes, size_t tab_cap);
+    /* Up to ring_bytes from `off` into ring[s] (64 zero bytes after them): the
+     * number of whole blocks at its front, tab[0 .. n) (in_off and c_off in
+     * ring[s], out_off from 0), as many as inflate to at most u_limit bytes but
+     * always one; *comp_len their bytes, *ubytes their inflated bytes; `off`
+     * moves past them.  0 at the end of the file, DD_READ_IO when the read
+     * failed, DD_READ_NOBLOCK when no whole block starts at `off` (`off` stays) */
+    int64_t read(int s, int64_t u_limit, int64_t *comp_len, int64_t *ubytes);
+};
+enum { DD_READ_IO = -1, DD_READ_NOBLOCK = -2 };
 #endif
 #endif

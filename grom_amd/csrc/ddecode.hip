@@ -8,6 +8,7 @@
 // as they are (20 GB per genome) and the GPU inflates them.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -15,12 +16,20 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <utility>
 #include <vector>
 #include <zlib.h>
 
 #include "../../include/grom_amd.h"
 #include "ddecode.h"
+#include "devbuf.h"
 #include "inflate.h"
+
+namespace {
+// growth slack: an eighth for small buffers, 1/64 for the run-sized ones
+// (reserved from estimates that carry their own margin)
+using DBuf = DevBufOf<GROM_DEVCAT_DECODE, 256, true>;
+}  // namespace
 
 #define DD_LANES 64
 #define DD_SLOTS 2   // compressed runs on the device (the prefetch thread's slots)
@@ -293,6 +302,49 @@ extern "C" int64_t dd_block_table_prefix(const uint8_t *buf, int64_t len, DdBloc
     return n;
 }
 
+// ---- a BGZF file read in whole blocks through two pinned ring buffers (ddecode.h) ----
+DdBgzfFile::DdBgzfFile(const char *path) : fp(fopen(path, "rb")) {
+    if (!fp) return;
+    fseeko(fp, 0, SEEK_END);
+    size = (int64_t)ftello(fp);
+    fseeko(fp, 0, SEEK_SET);
+}
+
+DdBgzfFile::~DdBgzfFile() {
+    for (uint8_t *r : ring)
+        if (r) (void)hipHostFree(r);
+    if (fp) fclose(fp);
+}
+
+int DdBgzfFile::rings(int64_t bytes, size_t tab_cap) {
+    ring_bytes = bytes;
+    tab.resize(tab_cap);
+    for (uint8_t *&r : ring) {
+        const hipError_t e = hipHostMalloc((void **)&r, (size_t)bytes + 64, 0);
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
+int64_t DdBgzfFile::read(int s, int64_t u_limit, int64_t *comp_len, int64_t *ubytes) {
+    *comp_len = *ubytes = 0;
+    if (off >= size) return 0;
+    const int64_t want = std::min<int64_t>(ring_bytes, size - off);
+    if (fseeko(fp, (off_t)off, SEEK_SET) != 0 || (int64_t)fread(ring[s], 1, (size_t)want, fp) != want) return DD_READ_IO;
+    memset(ring[s] + want, 0, 64);
+    int64_t ob = 0, used = 0;
+    const int64_t n = dd_block_table_prefix(ring[s], want, tab.data(), (int64_t)tab.size(), &ob, &used);
+    if (n <= 0) return DD_READ_NOBLOCK;
+    const int64_t have = std::min<int64_t>(n, (int64_t)tab.size());
+    int64_t nb = 0, ub = 0;
+    while (nb < have && (nb == 0 || ub + tab[(size_t)nb].out_len <= u_limit)) ub += tab[(size_t)nb++].out_len;
+    const DdBlock &lb = tab[(size_t)nb - 1];
+    *comp_len = lb.in_off + (int64_t)lb.in_len + 8;
+    *ubytes = ub;
+    off += *comp_len;
+    return nb;
+}
+
 // ---- test hook: every block of a BAM inflated on `device`, checked against zlib ----
 extern "C" int64_t grom_inflate_device_selftest(const char *bam_path, int device, int64_t max_bytes, int check,
                                                 double *ms_kernel, int64_t *n_blocks, int64_t *bytes) {
@@ -307,42 +359,25 @@ extern "C" int64_t grom_inflate_device_selftest(const char *bam_path, int device
     fclose(f);
     // whole blocks only (a prefix of the file)
     int64_t used = 0, ob = 0;
-    {
-        int64_t off = 0;
-        while (off + 18 <= size) {
-            const uint8_t *h = file.data() + off;
-            if (h[0] != 0x1f || h[1] != 0x8b) break;
-            const int xlen = rd16(h + 10);
-            int bsize = -1;
-            for (int o = 0; o + 4 <= xlen;) {
-                const int sl = rd16(h + 12 + o + 2);
-                if (h[12 + o] == 'B' && h[12 + o + 1] == 'C' && sl == 2) bsize = rd16(h + 12 + o + 4);
-                o += 4 + sl;
-            }
-            if (bsize < 0 || off + bsize + 1 > size) break;
-            off += bsize + 1;
-        }
-        used = off;
-    }
-    const int64_t nb = dd_block_table(file.data(), used, nullptr, 0, &ob);
+    const int64_t nb = dd_block_table_prefix(file.data(), size, nullptr, 0, &ob, &used);
     if (nb < 0) return -2;
     std::vector<DdBlock> tab((size_t)nb);
-    dd_block_table(file.data(), used, tab.data(), nb, &ob);
+    dd_block_table_prefix(file.data(), used, tab.data(), nb, &ob, &used);
     if (hipSetDevice(device) != hipSuccess) return -3;
-    uint8_t *d_comp = nullptr, *d_out = nullptr, *d_status = nullptr;
-    DdBlock *d_blk = nullptr;
-    uint32_t *d_bad = nullptr, *d_tok = nullptr;
     const size_t tok_bytes = dd_inflate_tok_bytes(nb);
     int64_t bad = -4;
     hipStream_t st = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipMalloc(&d_comp, (size_t)used + 64) != hipSuccess || hipMalloc(&d_out, (size_t)ob + 64) != hipSuccess ||
-        hipMalloc(&d_status, (size_t)nb + 1) != hipSuccess || hipMalloc(&d_blk, sizeof(DdBlock) * (size_t)(nb + 1)) != hipSuccess ||
-        hipMalloc(&d_bad, 8) != hipSuccess || (tok_bytes && hipMalloc(&d_tok, tok_bytes) != hipSuccess) ||
-        hipStreamCreate(&st) != hipSuccess || hipEventCreate(&e0) != hipSuccess ||
-        hipEventCreate(&e1) != hipSuccess)
+    // (accounted as decode memory: the hook runs in test processes, not in the CLI that prints the footprint)
+    DBuf b_comp, b_out, b_status, b_blk, b_bad, b_tok;
+    if (b_comp.grow((size_t)used + 64) || b_out.grow((size_t)ob + 64) || b_status.grow((size_t)nb + 1) ||
+        b_blk.grow(sizeof(DdBlock) * (size_t)(nb + 1)) || b_bad.grow(8) || (tok_bytes && b_tok.grow(tok_bytes)) ||
+        hipStreamCreate(&st) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
         goto done;
     {
+        uint8_t *d_comp = P<uint8_t>(b_comp), *d_out = P<uint8_t>(b_out), *d_status = P<uint8_t>(b_status);
+        DdBlock *d_blk = P<DdBlock>(b_blk);
+        uint32_t *d_bad = P<uint32_t>(b_bad), *d_tok = P<uint32_t>(b_tok);
         (void)hipMemcpyAsync(d_comp, file.data(), (size_t)used + 64, hipMemcpyHostToDevice, st);
         (void)hipMemcpyAsync(d_blk, tab.data(), sizeof(DdBlock) * (size_t)nb, hipMemcpyHostToDevice, st);
         (void)hipMemsetAsync(d_bad, 0, 8, st);
@@ -391,12 +426,6 @@ done:
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (st) (void)hipStreamDestroy(st);
-    (void)hipFree(d_comp);
-    (void)hipFree(d_out);
-    (void)hipFree(d_status);
-    (void)hipFree(d_blk);
-    (void)hipFree(d_bad);
-    (void)hipFree(d_tok);
     return bad;
 }
 
@@ -425,34 +454,20 @@ done:
 
 namespace {
 
-struct DBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
-
 std::atomic<int64_t> g_dgrow_ns{0};  // time in buffer growth (hipFree + hipMalloc), all contexts and stages
 
+// the decoder's growth, timed
 int dgrow(DBuf &b, size_t bytes, const char *what = nullptr) {
-    if (bytes == 0) bytes = 16;
-    if (b.cap >= bytes) return 0;
+    if (b.cap >= (bytes ? bytes : 16)) return 0;  // (nothing to grow: not timed)
     const auto t0 = std::chrono::steady_clock::now();
-    if (b.p) grom_dev_free(b.p, b.cap, GROM_DEVCAT_DECODE);
-    b.p = nullptr;
-    b.cap = 0;
-    // growth slack: an eighth for small buffers, 1/64 for the run-sized ones
-    // (reserved from estimates that carry their own margin)
-    const size_t want = bytes + (bytes >= ((size_t)64 << 20) ? bytes / 64 : bytes / 8) + 256;
-    const int e = grom_dev_malloc(&b.p, want, GROM_DEVCAT_DECODE);
+    const int e = b.grow(bytes);
     const int64_t ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
     g_dgrow_ns += ns;
     if (ns > 20000000 && getenv("GROM_VERBOSE"))
-        fprintf(stderr, "grom: device buffer %s of %.3f GB took %.1f ms\n", what ? what : "", (double)want / 1e9, ns / 1e6);
-    if (e != 0) return -1;
-    b.cap = want;
-    return 0;
+        fprintf(stderr, "grom: device buffer %s of %.3f GB took %.1f ms\n", what ? what : "", (double)b.want(bytes) / 1e9,
+                ns / 1e6);
+    return e;
 }
-
-template <class T> T *P(DBuf &b) { return (T *)b.p; }
 
 // bad-state bits
 enum : uint32_t { DB_INFLATE = 1, DB_CHAIN = 2, DB_RECORD = 4, DB_TID = 8, DB_UNSORTED = 16, DB_NAMES = 32,
@@ -1258,9 +1273,13 @@ __global__ void k_lower_bound(const int32_t *a, int64_t n, int32_t x, int64_t *o
 // one loaded run: its inflated bytes and record offsets, loaded on the slot's
 // own stream (the prefetch thread inflates and walks run k+1 while the worker
 // parses run k on the context's stream)
-struct RunSlot {
+// (the buffers are a base of their own so that dd_ctx_free can release them
+// in one assignment, before the slower teardown of streams and events)
+struct RunSlotBufs {
     DBuf U, blk, status, misc, S, ccnt, cbase, off, tmp;  // (blk, S: unused by the piece decode)
     DBuf tok;  // the two-phase inflate's tokens and per-block counts (dd_inflate_tok_bytes)
+};
+struct RunSlot : RunSlotBufs {
     hipStream_t st = nullptr;
     hipEvent_t ev[3] = {};
     int64_t *h_small = nullptr;  // pinned, mapped: k_piece_summary writes it
@@ -1269,7 +1288,17 @@ struct RunSlot {
     int64_t R = 0, nblk = 0, ubytes = 0;
 };
 
-struct dd_ctx {
+struct DdCtxBufs {
+    DBuf dcomp[DD_SLOTS];
+    DBuf misc;  // the parse's and the statistics' flags and scalars
+    DBuf keep, kidx, drop, didx, auxc, aidx, ncig, coff, nb, boff, rpos, krec, keys, vals, keys2, vals2, head, tmp;
+    DBuf srcs, tfq, tfs;  // per kept read: its bases' offset in U; per copy tile: its first read
+    DBuf sq, sqi, sv, slq, sm, s_ins, s_lq, acand, alen, aoff, akidx, apack;
+    DBuf rblk[DD_SLOTS], rS[DD_SLOTS];  // per compressed slot: the run's BGZF block table and record starts
+    DBuf nml, nmo, nm, nmoff;  // per piece record: name length, its offset; per chromosome: name bytes, offsets
+};
+
+struct dd_ctx : DdCtxBufs {
     int device = -1;
     RunSlot rs[DD_RSLOTS];
     int depth = 2;  // pieces in flight (GROM_DD_DEPTH, 1..DD_RSLOTS)
@@ -1296,18 +1325,11 @@ struct dd_ctx {
     int slot_busy[DD_SLOTS] = {};
     hipEvent_t tev = nullptr;  // the next run's tables uploaded on its piece slot's stream (issue_next)
     int trace = 0;             // GROM_DD_TRACE: one stderr line per fill and piece
-    DBuf dcomp[DD_SLOTS];
     hipEvent_t cev[DD_SLOTS] = {};
     int64_t dcomp_len[DD_SLOTS] = {};
     hipEvent_t ev[4] = {};
     hipEvent_t pev[DD_RSLOTS] = {};  // the piece in slot k is parsed (its U and record offsets are free)
     hipEvent_t rev[2] = {};         // the copy out of pinned ring buffer k is done (dd_comp_chunk)
-    DBuf misc;  // the parse's and the statistics' flags and scalars
-    DBuf keep, kidx, drop, didx, auxc, aidx, ncig, coff, nb, boff, rpos, krec, keys, vals, keys2, vals2, head, tmp;
-    DBuf srcs, tfq, tfs;  // per kept read: its bases' offset in U; per copy tile: its first read
-    DBuf sq, sqi, sv, slq, sm, s_ins, s_lq, acand, alen, aoff, akidx, apack;
-    DBuf rblk[DD_SLOTS], rS[DD_SLOTS];  // per compressed slot: the run's BGZF block table and record starts
-    DBuf nml, nmo, nm, nmoff;  // per piece record: name length, its offset; per chromosome: name bytes, offsets
     // inflated bytes per piece (GROM_DD_PIECE_MB): a launch of k_inflate takes
     // at least the time one lane needs for one block, so a piece must hold a
     // good part of a chip's worth of blocks (two pieces are in flight): 3 GB
@@ -1447,9 +1469,11 @@ extern "C" void dd_ctx_free(dd_ctx *c) {
     if (c->cst) (void)hipStreamSynchronize(c->cst);
     for (int k = 0; k < DD_RSLOTS; k++)
         if (c->rs[k].st) (void)hipStreamSynchronize(c->rs[k].st);
+    // the memory first (the scans still running wait for it), then the handles
+    for (RunSlot &r : c->rs) static_cast<RunSlotBufs &>(r) = RunSlotBufs();
+    static_cast<DdCtxBufs &>(*c) = DdCtxBufs();
     if (c->tev) (void)hipEventDestroy(c->tev);
     for (int k = 0; k < DD_SLOTS; k++) {
-        if (c->dcomp[k].p) grom_dev_free(c->dcomp[k].p, c->dcomp[k].cap, GROM_DEVCAT_DECODE);
         if (c->cev[k]) (void)hipEventDestroy(c->cev[k]);
         if (k < 2 && c->rev[k]) (void)hipEventDestroy(c->rev[k]);
     }
@@ -1457,22 +1481,11 @@ extern "C" void dd_ctx_free(dd_ctx *c) {
         if (c->pev[k]) (void)hipEventDestroy(c->pev[k]);
         RunSlot &r = c->rs[k];
         if (r.st) (void)hipStreamSynchronize(r.st);
-        DBuf *rb[] = {&r.U, &r.blk, &r.status, &r.misc, &r.S, &r.ccnt, &r.cbase, &r.off, &r.tmp, &r.tok};
-        for (DBuf *b : rb)
-            if (b->p) grom_dev_free(b->p, b->cap, GROM_DEVCAT_DECODE);
         for (int e = 0; e < 3; e++)
             if (r.ev[e]) (void)hipEventDestroy(r.ev[e]);
         if (r.h_small) (void)hipHostFree(r.h_small);
         if (r.st) (void)hipStreamDestroy(r.st);
     }
-    DBuf *all[] = {&c->misc, &c->keep,
-                   &c->kidx, &c->drop, &c->didx, &c->auxc, &c->aidx, &c->ncig, &c->coff, &c->nb, &c->boff, &c->rpos,
-                   &c->krec, &c->keys, &c->vals, &c->keys2, &c->vals2, &c->head, &c->tmp, &c->sq, &c->sqi, &c->sv,
-                   &c->srcs, &c->tfq, &c->tfs,
-                   &c->slq, &c->sm, &c->s_ins, &c->s_lq, &c->acand, &c->alen, &c->aoff, &c->akidx, &c->apack,
-                   &c->rblk[0], &c->rS[0], &c->rblk[1], &c->rS[1], &c->nml, &c->nmo, &c->nm, &c->nmoff};
-    for (DBuf *b : all)
-        if (b->p) grom_dev_free(b->p, b->cap, GROM_DEVCAT_DECODE);
     for (int k = 0; k < 4; k++)
         if (c->ev[k]) (void)hipEventDestroy(c->ev[k]);
     if (c->h_small) (void)hipHostFree(c->h_small);
@@ -1666,8 +1679,7 @@ static int dgrow_keep(DBuf &b, size_t bytes, size_t keep, hipStream_t st) {
             hipStreamSynchronize(st) != hipSuccess)
             return -1;
     }
-    if (b.p) grom_dev_free(b.p, b.cap, GROM_DEVCAT_DECODE);
-    b = nb;
+    b = std::move(nb);  // (frees the old block)
     return 0;
 }
 

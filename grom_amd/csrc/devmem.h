@@ -1,5 +1,8 @@
 /* devmem.h -- device memory of the library: every buffer the scan contexts,
- * stages and the BAM decoder grow is allocated here.
+ * stages, the BAM decoder, the index builder and the FASTA reader grow is
+ * allocated here.  The buffers themselves are DevBufs (devbuf.h: the one
+ * growable device buffer, on top of grom_dev_malloc, grom_dev_free and
+ * grom_arena_take below).
  *
  * One process per GPU holds a few large buffers per chromosome in flight
  * (DESIGN.md 3 and 8).  An allocation that fails does not fail the run at

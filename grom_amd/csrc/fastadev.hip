@@ -1,12 +1,14 @@
 // fastadev.hip -- the reference FASTA read on the device.
 //
 // The file's bytes are brought to the device once: a BGZF (bgzip) file is read
-// through two pinned buffers into HBM, its block table built on the host
-// (dd_block_table_prefix) and its blocks inflated by the decoder's inflater
-// (dd_inflate_launch, one block per lane) into one resident text; a plain file
-// is copied as it is.  The index (grom_fasta_open, stream.c) and the loader
-// (grom_fasta_load) are then kernels over that text, and give the host code's
-// results bit for bit.
+// in whole blocks through two pinned buffers into HBM (DdBgzfFile, ddecode.h,
+// which also builds each read's block table) and its blocks inflated by the
+// decoder's inflater (dd_inflate_launch, one block per lane) into one resident
+// text; a plain file is copied as it is.  The index (grom_fasta_open,
+// stream.c) and the loader (grom_fasta_load) are then kernels over that text,
+// and give the host code's results bit for bit.  The scratch of those kernels
+// is DevBufs (devbuf.h) accounted as decode memory, freed with the handle; the
+// text and the loaded references are plain allocations of their exact size.
 //
 // The host code reads with fgets(line, 1000).  Written without the sequential
 // read: a segment starts where reading starts or after a '\n'; a chunk starts
@@ -40,13 +42,8 @@
 
 #include "../../include/grom_amd.h"
 #include "ddecode.h"
-#include "devmem.h"
+#include "devbuf.h"
 #include "stream.h"
-
-extern "C" size_t dd_inflate_tok_bytes(int64_t n_blk);
-extern "C" int dd_inflate_launch(hipStream_t st, const uint8_t *d_comp, int64_t comp_cap, const DdBlock *d_blk,
-                                 int64_t n_blk, uint8_t *d_out, int64_t out_base, int64_t out_cap, uint8_t *d_status,
-                                 uint32_t *d_bad, uint32_t *d_bounds, uint32_t *d_tok, size_t tok_bytes);
 
 namespace {
 
@@ -290,23 +287,7 @@ __global__ void k_fa_copy(const uint8_t *__restrict__ T, int64_t a0, const int *
     }
 }
 
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
-template <class T> T *P(Buf &b) { return (T *)b.p; }
-
-int bgrow(Buf &b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.cap >= bytes) return 0;
-    if (b.p) grom_dev_free(b.p, b.cap, GROM_DEVCAT_DECODE);
-    b.p = nullptr;
-    b.cap = 0;
-    const size_t want = bytes + bytes / 8 + 256;
-    if (grom_dev_malloc(&b.p, want, GROM_DEVCAT_DECODE) != 0) return -1;
-    b.cap = want;
-    return 0;
-}
+using Buf = DevBufOf<GROM_DEVCAT_DECODE, 256>;  // decode memory, an eighth of slack (devbuf.h)
 
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -328,7 +309,13 @@ struct Win {
 
 }  // namespace
 
-struct grom_fasta_dev {
+// the kernels' scratch (a base of its own: grom_fasta_dev_close releases it in one assignment)
+struct FaScratch {
+    Buf tile_seg, tile_segs, tile_cnt, tile_base, cs, hdr, ca, cn, key, ks, al, pa, pn, pl, hidx, nsel, hrec, hbuf, small,
+        tmp;
+};
+
+struct grom_fasta_dev : FaScratch {
     int device = 0, bgzf = 0;
     int64_t piece = (int64_t)256 << 20;
     int64_t size = 0;  // the text's bytes
@@ -336,8 +323,6 @@ struct grom_fasta_dev {
     size_t text_cap = 0;
     hipStream_t st = nullptr;
     hipEvent_t ev[2] = {};
-    Buf tile_seg, tile_segs, tile_cnt, tile_base, cs, hdr, ca, cn, key, ks, al, pa, pn, pl, hidx, nsel, hrec, hbuf, small,
-        tmp;
     int64_t *h_small = nullptr;  // pinned
     std::vector<Entry> ent;
     int64_t mappable = 0;
@@ -365,7 +350,7 @@ struct grom_fasta_dev {
     } while (0)
 #define FAG(b, bytes)                                                                                              \
     do {                                                                                                           \
-        if (bgrow((b), (bytes))) return d->fail(GROM_E_NOMEM, "device FASTA: hipMalloc(%lld) failed", (long long)(bytes)); \
+        if ((b).grow(bytes)) return d->fail(GROM_E_NOMEM, "device FASTA: hipMalloc(%lld) failed", (long long)(bytes)); \
     } while (0)
 
 namespace {
@@ -384,28 +369,21 @@ int toc(grom_fasta_dev *d, double *acc) {
 // the file's bytes to the device: the text itself, or BGZF blocks inflated
 int ingest(grom_fasta_dev *d, const char *path) {
     const double t0 = now_ms();
-    FILE *fp = fopen(path, "rb");
-    if (!fp) return d->fail(GROM_E_ARG, "device FASTA: the file does not open");
-    struct Closer {
-        FILE *f;
-        uint8_t *ring[2] = {nullptr, nullptr};
+    DdBgzfFile R(path);  // (the plain file too: its FILE and ring buffers)
+    if (!R.fp) return d->fail(GROM_E_ARG, "device FASTA: the file does not open");
+    FILE *fp = R.fp;
+    const int64_t fsize = R.size;
+    // a ring buffer is read into again once its last copy is done
+    struct Events {
         hipEvent_t rev[2] = {};
-        ~Closer() {
-            fclose(f);
-            for (int k = 0; k < 2; k++) {
-                if (ring[k]) (void)hipHostFree(ring[k]);
-                if (rev[k]) (void)hipEventDestroy(rev[k]);
-            }
+        ~Events() {
+            for (hipEvent_t e : rev)
+                if (e) (void)hipEventDestroy(e);
         }
-    } C{fp};
-    fseeko(fp, 0, SEEK_END);
-    const int64_t fsize = (int64_t)ftello(fp);
-    fseeko(fp, 0, SEEK_SET);
+    } E;
     const int64_t ring = std::min<int64_t>(std::max<int64_t>(d->piece, 131072), (int64_t)64 << 20);
-    for (int k = 0; k < 2; k++) {
-        FAK(hipHostMalloc((void **)&C.ring[k], (size_t)ring + 64, 0));
-        FAK(hipEventCreateWithFlags(&C.rev[k], hipEventDisableTiming));
-    }
+    FAK((hipError_t)R.rings(ring, d->bgzf ? (size_t)(ring / 64 + 64) : 0));  // (a plain file has no block table)
+    for (int k = 0; k < 2; k++) FAK(hipEventCreateWithFlags(&E.rev[k], hipEventDisableTiming));
     if (!d->bgzf) {
         d->size = fsize;
         d->text_cap = (size_t)fsize + FA_TEXT_PAD;
@@ -414,12 +392,12 @@ int ingest(grom_fasta_dev *d, const char *path) {
         int64_t off = 0;
         for (int64_t k = 0; off < fsize; k++) {
             const int s = (int)(k & 1);
-            if (k >= 2) FAK(hipEventSynchronize(C.rev[s]));
+            if (k >= 2) FAK(hipEventSynchronize(E.rev[s]));
             const int64_t want = std::min<int64_t>(ring, fsize - off);
-            if ((int64_t)fread(C.ring[s], 1, (size_t)want, fp) != want)
+            if ((int64_t)fread(R.ring[s], 1, (size_t)want, fp) != want)
                 return d->fail(GROM_E_ARG, "device FASTA: read error at byte %lld", (long long)off);
-            FAK(hipMemcpyAsync(d->text + off, C.ring[s], (size_t)want, hipMemcpyHostToDevice, d->st));
-            FAK(hipEventRecord(C.rev[s], d->st));
+            FAK(hipMemcpyAsync(d->text + off, R.ring[s], (size_t)want, hipMemcpyHostToDevice, d->st));
+            FAK(hipEventRecord(E.rev[s], d->st));
             off += want;
         }
         FAK(hipStreamSynchronize(d->st));
@@ -428,39 +406,27 @@ int ingest(grom_fasta_dev *d, const char *path) {
     }
     // BGZF: the compressed file to HBM in whole blocks, the block table beside it
     Buf comp, dblk, status, tok, misc;
-    struct Freer {
-        Buf *b[5];
-        ~Freer() {
-            for (Buf *x : b)
-                if (x->p) grom_dev_free(x->p, x->cap, GROM_DEVCAT_DECODE);
-        }
-    } Fr{{&comp, &dblk, &status, &tok, &misc}};
     FAG(comp, (size_t)fsize + 64);
-    std::vector<DdBlock> tab((size_t)(ring / 64 + 64)), all;
-    int64_t foff = 0, total = 0;
-    for (int64_t k = 0; foff < fsize; k++) {
+    std::vector<DdBlock> all;
+    int64_t total = 0;
+    for (int64_t k = 0; R.off < fsize; k++) {
         const int s = (int)(k & 1);
-        if (k >= 2) FAK(hipEventSynchronize(C.rev[s]));
-        const int64_t want = std::min<int64_t>(ring, fsize - foff);
-        if (fseeko(fp, (off_t)foff, SEEK_SET) != 0 || (int64_t)fread(C.ring[s], 1, (size_t)want, fp) != want)
-            return d->fail(GROM_E_ARG, "device FASTA: read error at byte %lld", (long long)foff);
-        int64_t ob = 0, used = 0;
-        const int64_t n = dd_block_table_prefix(C.ring[s], want, tab.data(), (int64_t)tab.size(), &ob, &used);
+        if (k >= 2) FAK(hipEventSynchronize(E.rev[s]));
+        const int64_t foff = R.off;
+        int64_t clen = 0, ub = 0;  // (ub: not needed, the blocks are summed below)
+        const int64_t n = R.read(s, INT64_MAX, &clen, &ub);
+        if (n == DD_READ_IO) return d->fail(GROM_E_ARG, "device FASTA: read error at byte %lld", (long long)foff);
         if (n <= 0) return d->fail(GROM_E_ARG, "device FASTA: no whole BGZF block at byte %lld", (long long)foff);
-        const int64_t have = std::min<int64_t>(n, (int64_t)tab.size());
-        for (int64_t i = 0; i < have; i++) {
-            DdBlock b = tab[(size_t)i];
+        for (int64_t i = 0; i < n; i++) {
+            DdBlock b = R.tab[(size_t)i];
             b.in_off += foff;
             b.c_off += foff;
             b.out_off = total;
             total += b.out_len;
             all.push_back(b);
         }
-        const DdBlock &lb = tab[(size_t)have - 1];
-        const int64_t clen = lb.in_off + (int64_t)lb.in_len + 8;
-        FAK(hipMemcpyAsync(P<uint8_t>(comp) + foff, C.ring[s], (size_t)clen, hipMemcpyHostToDevice, d->st));
-        FAK(hipEventRecord(C.rev[s], d->st));
-        foff += clen;
+        FAK(hipMemcpyAsync(P<uint8_t>(comp) + foff, R.ring[s], (size_t)clen, hipMemcpyHostToDevice, d->st));
+        FAK(hipEventRecord(E.rev[s], d->st));
     }
     FAK(hipMemsetAsync(P<uint8_t>(comp) + fsize, 0, 64, d->st));
     FAK(hipStreamSynchronize(d->st));
@@ -678,10 +644,7 @@ extern "C" void grom_fasta_dev_close(grom_fasta_dev *d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     if (d->st) (void)hipStreamSynchronize(d->st);
-    Buf *all[] = {&d->tile_seg, &d->tile_segs, &d->tile_cnt, &d->tile_base, &d->cs, &d->hdr, &d->ca, &d->cn, &d->key, &d->ks,
-                  &d->al, &d->pa, &d->pn, &d->pl, &d->hidx, &d->nsel, &d->hrec, &d->hbuf, &d->small, &d->tmp};
-    for (Buf *b : all)
-        if (b->p) grom_dev_free(b->p, b->cap, GROM_DEVCAT_DECODE);
+    static_cast<FaScratch &>(*d) = FaScratch();
     for (auto &r : d->refs) grom_dev_free(r.first, r.second, GROM_DEVCAT_DECODE);
     if (d->text) grom_dev_free(d->text, d->text_cap, GROM_DEVCAT_DECODE);
     for (int k = 0; k < 2; k++)

@@ -36,6 +36,7 @@
 #include "../../include/grom_amd.h"
 #include "cnv.h"
 #include "ddecode.h"
+#include "devbuf.h"
 #include "sv.h"
 #include "scan_common.h"
 #include "snvfmt.h"
@@ -197,31 +198,13 @@ __global__ void k_flush_sum(int64_t e, const char *__restrict__ ref, const int32
 // ===========================================================================
 namespace {
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    bool own = false;          // p is this buffer's own allocation (else a piece of `ar`'s phase)
-    grom_arena *ar = nullptr;  // the context's phase arena, for the pileup phase's per-read buffers
-};
+using ScanBuf = DevBufOf<GROM_DEVCAT_SCAN, 64>;  // slack: kernels read whole 16-byte words
 
 static int ensure(DevBuf &b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.cap >= bytes) return GROM_OK;
-    if (b.p && b.own) grom_dev_free(b.p, b.cap, GROM_DEVCAT_SCAN);
-    b.p = nullptr;
-    b.cap = 0;
-    b.own = false;
-    size_t want = bytes + bytes / 8 + 64;  // slack: kernels read whole 16-byte words
-    if (b.ar && (b.p = grom_arena_take(b.ar, want)) != nullptr) {
-        b.cap = want;
-        return GROM_OK;
-    }
-    if (grom_dev_malloc(&b.p, want, GROM_DEVCAT_SCAN)) {
-        set_err("hipMalloc(%zu) failed", want);
+    if (b.grow(bytes)) {
+        set_err("hipMalloc(%zu) failed", b.want(bytes));
         return GROM_E_NOMEM;
     }
-    b.cap = want;
-    b.own = true;
     return GROM_OK;
 }
 
@@ -233,10 +216,10 @@ struct Ctx {
     grom_params prm{};
     double *d_mq = nullptr, *d_hez = nullptr;
     // reads (used when the caller passes host memory)
-    DevBuf r_pos, r_flag, r_mapq, r_mtid, r_mpos, r_isize, r_lq, r_coff, r_cig, r_boff, r_seq, r_qual, r_nid, ref;
-    DevBuf r_aidx, r_aux, r_dpos, r_dlq, r_dbef;
+    ScanBuf r_pos, r_flag, r_mapq, r_mtid, r_mpos, r_isize, r_lq, r_coff, r_cig, r_boff, r_seq, r_qual, r_nid, ref;
+    ScanBuf r_aidx, r_aux, r_dpos, r_dlq, r_dbef;
     // scan scratch
-    DevBuf keep, meta, tlo, thi, caf_mq, caf_rd, caf_low, cands, cands2, runb, runc, segs, misc, dbg, fpart, slots;
+    ScanBuf keep, meta, tlo, thi, caf_mq, caf_rd, caf_low, cands, cands2, runb, runc, segs, misc, dbg, fpart, slots;
     grom_snv_cand *h_cands = nullptr;  // pinned host copy of the ordered candidates
     unsigned long long *h_cafsum = nullptr, *d_cafsum = nullptr;  // mapped pinned word: k_caf_range_sum's result
     const char *host_ref = nullptr;    // the caller's host reference during grom_scan_chrom
@@ -253,7 +236,9 @@ struct Ctx {
     SvScratch *sv = nullptr;        // breakpoint evidence and tests (sv.hip)
 };
 
-static Ctx g_ctx[64];
+// never destroyed: a process that exits without grom_dev_fini must not free
+// device memory from a static destructor, after the runtime has shut down
+static Ctx *const g_ctx = new Ctx[64];
 
 static Ctx *ctx_of(int device) {
     if (device < 0 || device >= 64 || !g_ctx[device].init) {
@@ -430,15 +415,8 @@ static int scan_device(Ctx &C, const grom_chrom *ch, const grom_reads *R, grom_o
     }
     if (!C.sv) C.sv = sv_scratch_new();
     sv_scratch_phase(C.sv, par);
-    for (DevBuf *b : {&C.meta, &C.keep}) {
-        if (b->own && par) grom_dev_free(b->p, b->cap, GROM_DEVCAT_SCAN);
-        if (!b->own || par) {
-            b->p = nullptr;
-            b->cap = 0;
-            b->own = false;
-        }
-        b->ar = par;
-    }
+    C.meta.rebind(par);  // (the pileup phase's per-read buffers: the context's own phase list)
+    C.keep.rebind(par);
     int64_t n_eval = (a.eval_hi >= a.eval_lo) ? (int64_t)a.eval_hi - a.eval_lo + 1 : 0;
     if ((rc = ensure(C.tlo, sizeof(int32_t) * n_tiles)) || (rc = ensure(C.thi, sizeof(int32_t) * n_tiles)) ||
         (rc = ensure(C.caf_mq, sizeof(int32_t) * ch->len)) || (rc = ensure(C.caf_rd, sizeof(int32_t) * ch->len)) ||
@@ -1001,16 +979,6 @@ void grom_dev_fini(int device) {
     Ctx &C = g_ctx[device];
     (void)hipSetDevice(C.device);
     (void)hipStreamSynchronize(C.st);
-    DevBuf *all[] = {&C.r_pos, &C.r_flag, &C.r_mapq, &C.r_mtid, &C.r_mpos, &C.r_isize, &C.r_lq, &C.r_coff,
-                     &C.r_cig, &C.r_boff, &C.r_seq, &C.r_qual, &C.r_nid, &C.ref, &C.keep, &C.meta, &C.cands2,
-                     &C.runb, &C.runc, &C.segs, &C.fpart, &C.tlo, &C.thi, &C.caf_mq, &C.caf_rd, &C.caf_low, &C.cands,
-                     &C.misc, &C.dbg, &C.slots, &C.r_aidx, &C.r_aux, &C.r_dpos, &C.r_dlq, &C.r_dbef};
-    for (DevBuf *b : all)
-        if (b->p) {
-            if (b->own) grom_dev_free(b->p, b->cap, GROM_DEVCAT_SCAN);
-            b->p = nullptr;
-            b->cap = 0;
-        }
     if (C.h_cands) (void)hipHostFree(C.h_cands);
     if (C.h_cafsum) (void)hipHostFree(C.h_cafsum);
     if (C.st_copy) (void)hipStreamSynchronize(C.st_copy);
@@ -1027,7 +995,7 @@ void grom_dev_fini(int device) {
     (void)hipEventDestroy(C.ep0);
     (void)hipEventDestroy(C.ep1);
     (void)hipStreamDestroy(C.st);
-    g_ctx[device] = Ctx();
+    g_ctx[device] = Ctx();  // (frees the context's own buffers: both streams were drained above)
 }
 
 

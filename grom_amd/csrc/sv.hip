@@ -48,6 +48,7 @@
 
 #include "sv.h"
 #include "ddecode.h"
+#include "devbuf.h"
 #include "copystats.h"  // (GROM_COPY_STATS, last: it wraps the runtime copy calls)
 
 namespace {
@@ -920,12 +921,7 @@ __global__ void k_ctx_gather(const grom_sv_ctx *__restrict__ src, const uint32_t
     if (i < n) dst[i] = src[ord[i]];
 }
 
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-    bool own = false;          // p is this buffer's own allocation (else a piece of `ar`'s phase)
-    grom_arena *ar = nullptr;  // the context's phase arena (sv_scratch_phase), or none
-};
+using Buf = DevBufOf<GROM_DEVCAT_SV, 64>;  // (its arena: the context's phase arena, sv_scratch_phase)
 
 }  // namespace
 
@@ -942,23 +938,10 @@ struct SvScratch {
 };
 
 static int sbuf(Buf &b, size_t bytes, char *err, size_t errlen) {
-    if (bytes == 0) bytes = 16;
-    if (b.cap >= bytes) return GROM_OK;
-    if (b.p && b.own) grom_dev_free(b.p, b.cap, GROM_DEVCAT_SV);
-    b.p = nullptr;
-    b.cap = 0;
-    b.own = false;
-    const size_t want = bytes + bytes / 8 + 64;
-    if (b.ar && (b.p = grom_arena_take(b.ar, want)) != nullptr) {
-        b.cap = want;
-        return GROM_OK;
-    }
-    if (grom_dev_malloc(&b.p, want, GROM_DEVCAT_SV)) {
-        snprintf(err, errlen, "breakpoint pass: hipMalloc(%zu) failed", want);
+    if (b.grow(bytes)) {
+        snprintf(err, errlen, "breakpoint pass: hipMalloc(%zu) failed", b.want(bytes));
         return GROM_E_NOMEM;
     }
-    b.cap = want;
-    b.own = true;
     return GROM_OK;
 }
 
@@ -972,22 +955,11 @@ SvScratch *sv_scratch_new() { return new SvScratch(); }
 
 void sv_scratch_phase(SvScratch *s, grom_arena *ar) {
     Buf *all[] = SV_ALL_BUFS(s);
-    for (Buf *b : all) {
-        if (b->own && ar) grom_dev_free(b->p, b->cap, GROM_DEVCAT_SV);  // (an overflow of the last phase)
-        if (!b->own || ar) {
-            b->p = nullptr;
-            b->cap = 0;
-            b->own = false;
-        }
-        b->ar = ar;
-    }
+    for (Buf *b : all) b->rebind(ar);
 }
 
 void sv_scratch_free(SvScratch *s) {
     if (!s) return;
-    Buf *all[] = SV_ALL_BUFS(s);
-    for (Buf *b : all)
-        if (b->p && b->own) grom_dev_free(b->p, b->cap, GROM_DEVCAT_SV);
     if (s->h_hits) (void)hipHostFree(s->h_hits);
     if (s->e0) (void)hipEventDestroy(s->e0);
     if (s->e1) (void)hipEventDestroy(s->e1);
