@@ -35,6 +35,11 @@
 // chromosome depth variance of GROM.c:16664-16677 only feeds the repeat-bias
 // comparison (GROM.c:16765): it is bounded from an exact depth histogram, and
 // redone in base order on the host when the bound cannot decide.
+//
+// The host arithmetic of the "host" rows above is in cnvcall.cpp (no HIP, so
+// it is replayed on recorded inputs under sanitizers); the driver at the end
+// of this file (cnv_chrom: one function per phase) launches, copies and
+// calls into it.
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -52,36 +57,21 @@
 #include <vector>
 
 #include "cnv.h"
+#include "cnv_bisect.h"
+#include "cnvcall.h"
 #include "ddecode.h"
 #include "devbuf.h"
 #include "copystats.h"  // (GROM_COPY_STATS, last: it wraps the runtime copy calls)
 
 namespace {
 
-// ---- fixed parameters of the reference (not on its command line) ----
-constexpr int NBINS = 101;                 // g_num_gc_bins, GROM.c:947
-constexpr int REP_SEGS = 10;               // g_repeat_segments, GROM.c:732
-// g_sample_lists_len, GROM.c:725; GROM_SAMPLE_LISTS_LEN lowers it (test hook:
-// the reservoir draws of GROM.c:18292/18393 then fire on small inputs, and
-// the oracle reads the same variable)
-static long sample_len() {
-    const char *e = getenv("GROM_SAMPLE_LISTS_LEN");
-    const long x = e ? atol(e) : 0;
-    return (x > 0 && x < 100000) ? x : 100000L;
-}
-constexpr long REDUCTION = 1;              // g_genome_reduction_factor, GROM.c:726
-constexpr long BLOCK_FACTOR = 4;           // g_block_factor, GROM.c:738
-constexpr long BLOCK_UNIT = 10000;         // g_block_unit_size, GROM.c:740
-constexpr int MIN_ACGT = 99;               // g_insert_min_acgt, GROM.c:926
-constexpr long NO_COMBINE = 100;           // g_rd_no_combine_min_windows, GROM.c:929
-constexpr long RD_MIN_WINDOWS = 20;        // g_rd_min_windows, GROM.c:928
+// ---- fixed parameters of the reference (not on its command line; the ones
+// the host math shares are in cnvcall.h) ----
+using namespace cnvcall;
 constexpr int RD_MAX_MAPQ = 60;            // g_rd_max_mapq, GROM.c:718
 constexpr long MIN_RD_LOW_STDEV = 3;       // g_one_base_read_depth_min_rd_low_stdev, GROM.c:935
 constexpr double MAX_LOW_ACGT = 2;         // g_max_rd_low_acgt_or_windows, GROM.c:937
-constexpr double PLOIDY_NUM = 0.6;         // g_ploidy_threshold_numerator, GROM.c:939
-constexpr double STDEV_STEP = 0.01;        // g_stdev_step, GROM.c:940
 constexpr long MAX_DIST_LAST_GOOD = 10500; // default -X + 500, set before getopt (GROM.c:21898)
-constexpr int MAX_BLOCK_LIST = 10000;      // max_block_list_len, GROM.c:633
 
 constexpr int GC_TP = 16384;               // positions per k_cnv_gc tile
 constexpr int GC_MMAX_S = 1536;            // k_cnv_gc<GC_MMAX_S>: 32-bit window arithmetic
@@ -90,20 +80,7 @@ template <int MMAX>
 constexpr int gc_nw() { return (GC_TP + 2 * MMAX + 1 + 63) / 64; }  // 64-bit class words per tile (with halo)
 constexpr int SEG_W = 4096;                // positions per wave in the state scans
 constexpr int ZT_MAX = 1024;               // depths with a precomputed z rank index
-constexpr int HIST_MAX = 4096;             // exact depth histogram for the chromosome variance
 constexpr int64_t WALK_CHUNK = 16384;      // positions per speculative walk lane
-
-// flag byte per position
-constexpr uint8_t F_LOW = 1;    // ddd_rd_low_acgt_or_windows_list != 0
-constexpr uint8_t F_GUARD = 2;  // z-scored / windowed base (GROM.c:18765 condition)
-
-struct Tables {  // device copy of the per-chromosome bin statistics
-    int32_t off[2][NBINS], cnt[2][NBINS];
-    int64_t wins[2][NBINS];
-    double ave[2][NBINS], sdv[2][NBINS], thr[2][2][NBINS];  // thr[0]=del, thr[1]=dup
-    double p2s_p[1001], p2s_sd[1001];
-    int32_t n_p2s;
-};
 
 struct Args {
     int64_t len, lo, hi;  // [lo, hi) = [insert_mean-1, len - window_size)
@@ -249,11 +226,6 @@ __global__ __launch_bounds__(256) void k_cnv_gc(const char *__restrict__ ref, Ar
     }
 }
 
-struct RepeatRec {
-    int64_t start, end, rd;  // [start, end), depth sum over it
-    int32_t type, pad;
-};
-
 // Repeat runs (GROM.c:1727-1768): a maximal run of one class, closed before
 // the last scanned base, of at least g_min_repeat bases.
 __global__ void k_cnv_repeats(const uint8_t *__restrict__ rtype, const int32_t *__restrict__ rd,
@@ -320,10 +292,6 @@ __global__ __launch_bounds__(256) void k_cnv_blocks(const char *__restrict__ ref
     for (int i = threadIdx.x; i <= HIST_MAX; i += 256)
         if (h[i]) atomicAdd(&hist[i], h[i]);
 }
-
-struct GatherRange {
-    int64_t start, count, stride, out;
-};
 
 // per-position values for host-side steps (sampling, copy number)
 __global__ void k_cnv_gather(const GatherRange *__restrict__ rg, int n_rg, const uint8_t *__restrict__ gcw,
@@ -469,41 +437,6 @@ __global__ __launch_bounds__(256) void k_cnv_flags(Args A, const uint8_t *__rest
     }
 }
 
-// GROM.c:21630-21860, exact
-__device__ long d_bisect_left(const int *l, int rd, long s, long e) {
-    int found = 0;
-    long i = s + (e - s) / 2, lo = s, hi = e;
-    while (found == 0) {
-        if (i <= s) { i = (rd <= l[s]) ? s : s + 1; found = 1; }
-        else if (i >= e - 1) { i = (rd <= l[e - 1]) ? e - 1 : e; found = 1; }
-        else if (rd <= l[i]) { hi = i; i = lo + (i - lo) / 2; if (hi == i) { found = 1; i += 1; } }
-        else { lo = i; i = i + (hi - i) / 2; if (lo == i) { found = 1; i += 1; } }
-    }
-    return i;
-}
-__device__ long d_bisect_right(const int *l, int rd, long s, long e) {
-    int found = 0;
-    long i = s + (e - s) / 2, lo = s, hi = e;
-    while (found == 0) {
-        if (i <= s) { i = (rd < l[s]) ? s : s + 1; found = 1; }
-        else if (i >= e - 1) { i = (rd < l[e - 1]) ? e - 1 : e; found = 1; }
-        else if (rd < l[i]) { hi = i; i = lo + (i - lo) / 2; if (hi == i) { found = 1; i += 1; } }
-        else { lo = i; i = i + (hi - i) / 2; if (lo == i) { found = 1; i += 1; } }
-    }
-    return i;
-}
-__device__ long d_bisect_right_double(const double *l, double p, long s, long e) {
-    int found = 0;
-    long i = s + (e - s) / 2, lo = s, hi = e;
-    while (found == 0) {
-        if (i <= s) { i = (p < l[s]) ? s : s + 1; found = 1; }
-        else if (i >= e - 1) { i = (p < l[e - 1]) ? e - 1 : e; found = 1; }
-        else if (p < l[i]) { hi = i; i = lo + (i - lo) / 2; if (hi == i) { found = 1; i += 1; } }
-        else { lo = i; i = i + (hi - i) / 2; if (lo == i) { found = 1; i += 1; } }
-    }
-    return i;
-}
-
 // z-score rank index for every (class, bin, depth < ZT_MAX) (ranks mode):
 // the two bisects into the sorted bin sample and the pval2sd bisect of
 // GROM.c:18800-18940 depend on nothing else.  Entry: +/-(pval2sd index + 1)
@@ -517,16 +450,16 @@ __device__ int z_rank_index(const Tables *T, const int32_t *samples, int mqi, in
     double d1, d2, prob;
     int sign = 1;
     if (r < ave) {
-        i1 = d_bisect_right(list, r, 0, ge);
-        i2 = d_bisect_left(list, r, 0, ge);
+        i1 = cnv_bisect_right(list, r, 0, ge);
+        i2 = cnv_bisect_left(list, r, 0, ge);
     } else {
         sign = -1;
         if (r > dup_factor * ave) {
-            i1 = d_bisect_left(list, (int)(dup_factor * ave), 0, ge);  // Q11 truncation
-            i2 = d_bisect_right(list, r, 0, ge);
+            i1 = cnv_bisect_left(list, (int)(dup_factor * ave), 0, ge);  // Q11 truncation
+            i2 = cnv_bisect_right(list, r, 0, ge);
         } else {
-            i1 = d_bisect_left(list, r, 0, ge);
-            i2 = d_bisect_right(list, r, 0, ge);
+            i1 = cnv_bisect_left(list, r, 0, ge);
+            i2 = cnv_bisect_right(list, r, 0, ge);
         }
         i1 = ge - i1;
         i2 = ge - i2;
@@ -534,7 +467,7 @@ __device__ int z_rank_index(const Tables *T, const int32_t *samples, int mqi, in
     d1 = (i1 <= 0) ? 0.5 : (double)i1;
     d2 = (i2 <= 0) ? 0.5 : (double)i2;
     prob = (d1 + d2) / (2 * ge);
-    i1 = d_bisect_right_double(T->p2s_p, prob, 0, T->n_p2s);
+    i1 = cnv_bisect_right_double(T->p2s_p, prob, 0, T->n_p2s);
     if (i1 < 0) i1 = 0;
     else if (i1 >= T->n_p2s) i1 = T->n_p2s - 1;
     return sign * (int)(i1 + 1);
@@ -596,14 +529,6 @@ __global__ __launch_bounds__(256) void k_cnv_z(Args A, const uint8_t *__restrict
 // window is a run of pieces of consecutive bases (it straddles the sampling
 // passes of a block: as many as -A when a block is short for -X).  out row:
 // [min_len..len] means, NaN = none.
-struct WinPiece {
-    int64_t start, count;
-};
-struct WinDesc {
-    int64_t p0, n0, p1, n1, p2, n2;  // the first three pieces inline (the common case)
-    int64_t piece0, n_pieces, ntot;  // all pieces: [piece0, piece0 + n_pieces) of the piece list, ntot bases
-    int64_t row;
-};
 // Window means for every length (GROM.c:18967-19018).  Each window's running
 // sums are one sequential chain in the reference's order, so one lane owns a
 // window; what made the one-lane form slow was everything else per base (two
@@ -779,12 +704,6 @@ __global__ __launch_bounds__(256) void k_cnv_gen1000(const uint8_t *__restrict__
 }
 
 // ---------------- DEL / DUP window search (GROM.c:19359-20020) ----------------
-struct CallRec {
-    int64_t p, ce;
-    double stdevs;
-    int32_t m, pad;
-};
-
 // per-position bit word the walk reads (one uint16 instead of five arrays)
 constexpr uint32_t B_LOW = 1, B_HI = 2, B_RTP = 4, B_DEL0 = 8, B_DUP0 = 32, B_W0 = 128;
 
@@ -2798,194 +2717,10 @@ __device__ __forceinline__ int first_passage(uint64_t P, int n, int e, const Cls
 // far above that difference is UNDECIDED and computed exactly (k_cnv_pre or
 // the walk), so the jumps and no-ops written are exact.
 //
-// The work per candidate ranges from one word (a jump near its start) to
-// L/64 = 157 words (a no-op window), so the lanes do not stay with one
-// candidate: each takes one segment per step and, when its candidate is
-// decided, the next candidate from the wave's share of a global queue (one
-// atomic per CLS_GRAB candidates).  A wave runs until the queue
-// is empty and its lanes are idle, instead of waiting at every candidate for
-// its slowest lane.
-
-// candidates a wave takes from the global queue at a time
-constexpr uint32_t CLS_GRAB = 128;
-
-template <int KIND>
-__global__ __launch_bounds__(256) void k_cnv_classify(WalkIn W, const int64_t *__restrict__ cand, uint32_t n_cand,
-                                                      CandWords C, const double *__restrict__ wsdmin,
-                                                      int32_t *__restrict__ nxt, int64_t *__restrict__ und,
-                                                      uint32_t *n_und, uint32_t und_cap, uint32_t *__restrict__ qhead) {
-    __shared__ ClsTabs T;
-    // GROM_TIMING counters (W.stats + 24): candidates, phase-A jumps, first
-    // window undecided, passing bases tested one by one, segments settled by
-    // the bound, phase-B undecided, no-ops, segments tested base by base
-    __shared__ unsigned long long cst[8];
-    cls_tabs_build(T);
-    if (W.stats && threadIdx.x < 8) cst[threadIdx.x] = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int64_t L = W.L, ML = W.min_len, end = W.end, nw = C.n_words;
-    const double sgn = KIND == 0 ? 1.0 : -1.0;
-    unsigned long long c_steps = 0, c_skip = 0, c_wstep = 0, c_n[4] = {0, 0, 0, 0};  // jump, first undecided, B undecided, no-op
-    // the lane's candidate
-    uint32_t ci = 0;
-    bool busy = false;
-    int64_t p = 0, lo = 0, wl = 0, cnt = 0;
-    int m = 0, E = 0, phase = 0;  // phase 0: A, 1: B
-    bool defined = false;
-    double R = 0.0, A = 0.0;
-    bool drained = false;
-    uint32_t qb = 0, qe = 0;  // the wave's share of the queue not yet handed to a lane (wave-uniform)
-    for (;;) {
-        // refill the idle lanes: from the wave's share, then (one atomic per
-        // CLS_GRAB candidates) a new share
-        unsigned long long idle = __ballot(!busy);
-        for (int pass = 0; pass < 2 && idle && !drained; pass++) {
-            if (qb >= qe) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(qhead, (uint32_t)CLS_GRAB);
-                base = (uint32_t)__shfl((int)base, 0);
-                if (base >= n_cand) {
-                    drained = true;
-                    break;
-                }
-                qb = base;
-                qe = min(base + (uint32_t)CLS_GRAB, n_cand);
-            }
-            const uint32_t avail = qe - qb, n_idle = (uint32_t)__popcll(idle);
-            const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1));
-            if (!busy && rank < avail) {
-                ci = qb + rank;
-                busy = true;
-                p = cand[ci] >> 1;
-                m = (int)(cand[ci] & 1);
-                lo = p;
-                wl = cnt = 0;
-                E = 0;
-                phase = 0;
-                defined = false;
-                R = A = 0.0;
-            }
-            qb += min(n_idle, avail);
-            idle = __ballot(!busy);
-        }
-        if (!__ballot(busy)) break;
-        if (!busy) continue;
-        // one segment of the lane's candidate
-        const uint64_t *pmw = C.pm + (KIND * 2 + m) * nw, *pkw = C.pk + KIND * nw;
-        int outcome = -2;  // -2 running, 0 jump (out set), 1 first-window undecided, 2 B undecided, 3 no-op
-        int32_t out = (int32_t)p;
-        const int64_t lim = phase == 0 ? p + ML : min(p + L, end);
-        if (lo >= lim) {
-            outcome = 3;  // phase B reached its end (or an empty window): no stop, no call
-        } else {
-            const int64_t w = lo >> 6, hi = min(lim, (w + 1) << 6);
-            const int s0 = (int)(lo & 63), n = (int)(hi - lo);
-            const uint64_t M = low_bits(n) << s0;
-            uint64_t P;
-            if (defined) {
-                P = pkw[w] & M;
-            } else {
-                const uint64_t dw = C.def[w] & M;
-                if (!dw) {
-                    P = pmw[w] & M;
-                } else {
-                    const uint64_t below = (dw & (0 - dw)) - 1;
-                    defined = true;
-                    P = ((pmw[w] & below) | (pkw[w] & ~below)) & M;
-                }
-            }
-            const int j = first_passage(P >> s0, n, E, T);
-            if (phase == 0) {
-                if (j < n) {  // the stop: the walk jumps here
-                    out = (int32_t)(lo + j);
-                    outcome = 0;
-                } else {
-                    E += 2 * (int)__popcll(P) - n;
-                    wl += n;
-                    cnt += __popcll(C.nl[w] & M);
-                    R += sgn * (C.rsa[hi - 1] - (s0 ? C.rsa[lo - 1] : 0.0));
-                    A += C.babs[w];
-                    lo = hi;
-                    if (lo == p + ML) {
-                        // the first window's z test (every base's z, nonlow count)
-                        if (cnt > 0 && W.wsd[ML] > 0) {
-                            const double d = (double)cnt * W.wsd[ML];
-                            if (!(R + 1e-9 * (A + fabs(R)) + 1e-300 < 3.0 * d * (1.0 - 1e-15))) outcome = 1;
-                        }
-                        phase = 1;
-                    }
-                }
-            } else {
-                const uint64_t Pr = (P >> s0) & low_bits(j);  // passing bases before the stop
-                const double base = s0 ? C.rsn[lo - 1] : 0.0;
-                if (Pr) {
-                    const double ub = KIND == 0 ? R + (C.bmax[w] - base) : R - (C.bmin[w] - base);
-                    const double dlo = (double)(cnt + 1) * wsdmin[wl + 1];
-                    const double slack = 1e-9 * (A + C.babs[w] + fabs(ub)) + 1e-300;
-                    if (dlo > 0 && ub + slack < 3.0 * dlo * (1.0 - 1e-15)) {
-                        c_skip++;
-                    } else {
-                        c_wstep++;
-                        const uint64_t nlr = C.nl[w] >> s0;
-                        for (uint64_t q = Pr; q; q &= q - 1) {
-                            const int k = __ffsll((long long)q) - 1;
-                            const double Rk = R + sgn * (C.rsn[lo + k] - base);
-                            const int64_t ck = cnt + __popcll(nlr & low_bits(k + 1));
-                            const double ws = W.wsd[wl + k + 1];
-                            c_steps++;
-                            if (ws > 0) {
-                                const double d = (double)ck * ws;
-                                if (!(Rk + 1e-9 * (A + C.babs[w] + fabs(Rk)) + 1e-300 < 3.0 * d * (1.0 - 1e-15))) {
-                                    outcome = 2;
-                                    break;
-                                }
-                            }
-                        }
-                    }
-                }
-                if (outcome < 0) {
-                    if (j < n) {
-                        outcome = 3;  // phase B stops without a call: no-op
-                    } else {
-                        E += 2 * (int)__popcll(P) - n;
-                        wl += n;
-                        cnt += __popcll(C.nl[w] & M);
-                        R += sgn * (C.rsn[hi - 1] - base);
-                        A += C.babs[w];
-                        lo = hi;
-                    }
-                }
-            }
-        }
-        if (outcome >= 0) {
-            if (outcome == 1 || outcome == 2) {
-                out = NXT_UNDECIDED;
-                const uint32_t k = atomicAdd(n_und, 1u);
-                if (k < und_cap) und[k] = cand[ci];
-            }
-            nxt[m * W.len + p] = out;
-            c_n[outcome]++;
-            busy = false;
-        }
-    }
-    if (W.stats) {
-        atomicAdd(&cst[0], c_n[0] + c_n[1] + c_n[2] + c_n[3]);
-        atomicAdd(&cst[1], c_n[0]);
-        atomicAdd(&cst[2], c_n[1]);
-        atomicAdd(&cst[5], c_n[2]);
-        atomicAdd(&cst[6], c_n[3]);
-        atomicAdd(&cst[3], c_steps);
-        atomicAdd(&cst[4], c_skip);
-        atomicAdd(&cst[7], c_wstep);
-        __syncthreads();
-        if (threadIdx.x < 8) atomicAdd(W.stats + 24 + threadIdx.x, cst[threadIdx.x]);
-    }
-}
-
-// The same classification with one lane per candidate for its whole window
-// (the default; GROM_CNV_CLS=1 takes the queue kernel above): lanes of a wave
-// walk neighbouring candidates in step, so their word loads coalesce, but a
-// wave waits for its longest candidate.  Measured faster than the queue.
+// A lane keeps its candidate for the whole window: lanes of a wave walk
+// neighbouring candidates in step, so their word loads coalesce, but a wave
+// waits for its longest candidate (one word for a jump near its start,
+// L/64 = 157 words for a no-op window).
 template <int KIND>
 __global__ __launch_bounds__(256) void k_cnv_classify_lane(WalkIn W, const int64_t *__restrict__ cand, uint32_t n_cand,
                                                       CandWords C, const double *__restrict__ wsdmin,
@@ -3235,112 +2970,12 @@ static int grow(Buf &b, size_t bytes, char *err, size_t errlen) {
     return GROM_OK;
 }
 
-// glibc random()/rand() (TYPE_3, stdlib/random_r.c) for grom_rand, GROM.c:1185
-struct GlibcRand {
-    int32_t st[31];
-    int f = 3, r = 0;
-    explicit GlibcRand(uint32_t seed) {
-        if (seed == 0) seed = 1;
-        st[0] = (int32_t)seed;
-        int32_t word = (int32_t)seed;  // int32_t in glibc's __srandom_r
-        for (int i = 1; i < 31; i++) {
-            long hi = word / 127773, lo = word % 127773;
-            word = (int32_t)(16807 * lo - 2836 * hi);
-            if (word < 0) word += 2147483647;
-            st[i] = word;
-        }
-        for (int i = 0; i < 310; i++) next();
-    }
-    int next() {
-        uint32_t v = (uint32_t)st[f] + (uint32_t)st[r];
-        st[f] = (int32_t)v;
-        if (++f >= 31) { f = 0; ++r; } else if (++r >= 31) r = 0;
-        return (int)(v >> 1);
-    }
-    long grom_rand(long mx) {  // GROM.c:1185-1201
-        long v = 0, c = 1, t;
-        while (c < mx) {
-            t = (next() % 10) * c;
-            while (t + v >= mx) t = (next() % 10) * c;
-            v += t;
-            c *= 10;
-        }
-        return v;
-    }
-};
-
-// qsort(double[], cmpfunc) of glibc 2.12 (msort.c) with the reference's int
-// comparator reading each double's low 32 bits
-static int dcmp_lo(double a, double b) {
-    uint32_t x, y;
-    memcpy(&x, &a, 4);
-    memcpy(&y, &b, 4);
-    return (int32_t)(x - y);
-}
-static void msort_lo(double *b, size_t n, double *t) {
-    if (n <= 1) return;
-    size_t n1 = n / 2, n2 = n - n1;
-    double *b1 = b, *b2 = b + n1;
-    msort_lo(b1, n1, t);
-    msort_lo(b2, n2, t);
-    double *o = t;
-    while (n1 > 0 && n2 > 0) {
-        if (dcmp_lo(*b1, *b2) <= 0) { *o++ = *b1++; --n1; }
-        else { *o++ = *b2++; --n2; }
-    }
-    if (n1 > 0) memcpy(o, b1, n1 * sizeof(double));
-    memcpy(b, t, (n - n2) * sizeof(double));
-}
-
-// the same merge sort with the two halves of the top `depth` levels sorted on
-// their own threads (each with its own half of the scratch): the same
-// operations on the same data, so the same order -- which matters, since the
-// reference's comparator (low 32 bits, wrapping difference) is not a total
-// order and only this exact merge sequence reproduces its result
-static void msort_lo_par(double *b, size_t n, double *t, int depth) {
-    if (depth <= 0 || n < (1u << 16)) {
-        msort_lo(b, n, t);
-        return;
-    }
-    size_t n1 = n / 2, n2 = n - n1;
-    double *b1 = b, *b2 = b + n1;
-    std::thread th([=] { msort_lo_par(b1, n1, t, depth - 1); });
-    msort_lo_par(b2, n2, t + n1, depth - 1);
-    th.join();
-    double *o = t;
-    while (n1 > 0 && n2 > 0) {
-        if (dcmp_lo(*b1, *b2) <= 0) { *o++ = *b1++; --n1; }
-        else { *o++ = *b2++; --n2; }
-    }
-    if (n1 > 0) memcpy(o, b1, n1 * sizeof(double));
-    memcpy(b, t, (n - n2) * sizeof(double));
-}
-
-// sort of small non-negative ints (read depths): counting sort, same result
-// as the reference's qsort with cmpfunc on these values
-static void sort_depths(std::vector<int> &v) {
-    if (v.size() < 2) return;
-    int mx = 0;
-    for (int x : v) {
-        if (x < 0) { std::sort(v.begin(), v.end()); return; }
-        mx = std::max(mx, x);
-    }
-    if (mx > (1 << 20)) { std::sort(v.begin(), v.end()); return; }
-    std::vector<uint32_t> h((size_t)mx + 1, 0);
-    for (int x : v) h[x]++;
-    size_t k = 0;
-    for (int x = 0; x <= mx; x++)
-        for (uint32_t c = 0; c < h[x]; c++) v[k++] = x;
-}
-
 // Per-position values of gathered ranges on the host, views of one pinned
 // buffer the device copy lands in (round 5 copied 15 bytes per position into
 // a zero-filled pageable vector and split it into six more: 54-74 ms per
 // chromosome for the copy numbers' ~6 M positions); rt = rd + low is made on
 // the device.  The buffer goes back to the scratch's pool with the view.
-struct Gathered {
-    const uint8_t *gc = nullptr, *ac = nullptr, *flag = nullptr;
-    const int32_t *mq = nullptr, *rd = nullptr, *low = nullptr, *rt = nullptr;
+struct Gathered : GatherView {
     CnvScratch::PinBuf *pb = nullptr;
     Gathered() = default;
     Gathered(const Gathered &) = delete;
@@ -3461,10 +3096,11 @@ __global__ void k_cnv_gc_global(const char *__restrict__ ref, Args A, int64_t m,
     }
 }
 
-// test hook GROM_GC_GLOBAL=1: the prefix form at any insert mean
+// test hook GROM_GC_GLOBAL=1: the prefix form at any insert mean (read at every
+// call: the tests set it for single scans of one process)
 static bool gc_global_forced() {
-    static const bool f = getenv("GROM_GC_GLOBAL") && atoi(getenv("GROM_GC_GLOBAL")) == 1;
-    return f;
+    const char *e = getenv("GROM_GC_GLOBAL");
+    return e && atoi(e) == 1;
 }
 
 // GC/ACGT weights and dinucleotide classes depend on the reference alone
@@ -3538,32 +3174,138 @@ void cnv_scratch_free(CnvScratch *S) {
     delete S;
 }
 
-int cnv_chrom(CnvScratch *S, hipStream_t st, const grom_params &P, uint32_t seed, const char *chr_name,
-              const char *d_ref, int64_t len, int32_t *d_mq, const int32_t *d_rd, const int32_t *d_low,
-              std::string &rows, CnvTiming *timing, char *err, size_t errlen, std::string *side) {
-    const auto t_host0 = std::chrono::steady_clock::now();
-    int rc;
-    const int64_t m = P.insert_mean, W = 2 * (int64_t)m - 1;
-    const int64_t total_w = (int64_t)m * m;  // g_one_base_window_size_total, GROM.c:22265-22269
-    if (m < 1) {
-        snprintf(err, errlen, "insert mean %lld below 1", (long long)m);
-        return GROM_E_ARG;
-    }
-    // (window lengths index int32 positions in the walk; -X past a chromosome
-    // only makes every window search stop at the end)
-    if (P.max_rd_window_len < P.min_rd_window_len || P.min_rd_window_len < 1 || P.windows_sampling_factor < 1 ||
-        P.max_rd_window_len > ((int64_t)1 << 30)) {
-        snprintf(err, errlen, "unsupported CNV window parameters (-W %lld -X %lld -A %lld)",
-                 (long long)P.min_rd_window_len, (long long)P.max_rd_window_len, (long long)P.windows_sampling_factor);
-        return GROM_E_ARG;
-    }
-    if ((rc = cnv_init(S, err, errlen))) return rc;
-    GlibcRand rng(seed);
+namespace {
+
+// ---- host-side layouts of the small device blocks the kernels get word
+// addresses into ----
+
+// S->misc (cleared per chromosome)
+struct MiscWords {
+    unsigned long long acc[4];  // k_cnv_blocks: block depth sum and count, chromosome depth sum and count
+    unsigned long long unused[4];
+    uint32_t n_rep;             // k_cnv_repeats: repeats listed
+    uint32_t unused2[15];
+};
+static_assert(offsetof(MiscWords, n_rep) == 64 && sizeof(MiscWords) == 128, "k_cnv_blocks / k_cnv_repeats word addresses");
+
+// GROM_TIMING counters of one kind's window search (WalkIn::stats; the
+// kernels index it as 64-bit slots)
+struct WalkStats {
+    unsigned long long mode[4][5];     // per walk mode (0, 1, repairs, resumed): wave A/B, wave C/D, slide rounds, trim rounds, stops
+    unsigned long long longest[2];     // longest resumed slide: steps, wall-clock ticks
+    unsigned long long unused[2];
+    unsigned long long classify[8];    // slot 24, k_cnv_classify_lane
+    unsigned long long cls_blocks[4];  // slot 32: aligned blocks reached, with known pass bits, walk clear, skipped
+    unsigned long long unused2[4];
+    unsigned long long prof[9];        // slot 40: slide clock counters (WalkIn::prof)
+    unsigned long long unused3[7];
+};
+// K.cnt: one kind's counters, cleared per attempt up to n_und
+struct KindCounters {
+    uint32_t n_calls, n_pre, n_cand, n_capped, n_und;  // calls, call starts, candidates, capped call starts, undecided
+    uint32_t unused[3];
+    uint32_t n_fix;  // chunks repaired by k_cnv_reconcile
+    uint32_t unused2[7];
+    WalkStats stats;
+};
+static_assert(offsetof(KindCounters, n_fix) == 32 && offsetof(KindCounters, stats) == 64 && sizeof(KindCounters) == 512 &&
+                  offsetof(WalkStats, classify) == 24 * 8 && offsetof(WalkStats, cls_blocks) == 32 * 8 &&
+                  offsetof(WalkStats, prof) == 40 * 8,
+              "the word addresses the walk kernels count into");
+
+// The classification's word arrays, laid out from `base` (a 64-byte aligned
+// block; null: nothing is assigned).  Returns the bytes the block needs, so
+// one routine sizes it and places the pointers.
+size_t carve_cand_words(CandWords &CW, char *base, int64_t n_words, int64_t n_sup, int64_t L) {
+    size_t off = 0, pad = 0;
+    auto take = [&](size_t bytes) {
+        char *p = base ? base + off : nullptr;
+        off += bytes;
+        return p;
+    };
+    const size_t w = (size_t)n_words;
+    CW.n_words = n_words;
+    CW.nl = (uint64_t *)take(8 * w);
+    CW.def = (uint64_t *)take(8 * w);
+    CW.pm = (uint64_t *)take(8 * 4 * w);
+    CW.pk = (uint64_t *)take(8 * 2 * w);
+    CW.defa = (uint64_t *)take(8 * w);
+    CW.c1a = (uint64_t *)take(8 * w);
+    CW.c1n = (uint64_t *)take(8 * w);
+    CW.pa = (uint64_t *)take(8 * 4 * w);
+    CW.bsum = (double *)take(8 * w);
+    CW.bmax = (double *)take(8 * w);
+    CW.bmin = (double *)take(8 * w);
+    CW.babs = (double *)take(8 * w);
+    CW.rsn = (double *)take(8 * 64 * w);
+    CW.rsa = (double *)take(8 * 64 * w);
+    CW.bmax4 = (double *)take(8 * 4 * w);
+    CW.bmin4 = (double *)take(8 * 4 * w);
+    CW.kend = (int8_t *)take(w);
+    pad = ((off + 63) & ~(size_t)63) - off;  // sup starts on a 64-byte line
+    off += pad;
+    CW.n_sup = n_sup;
+    CW.sup = (SuperW *)take(sizeof(SuperW) * (size_t)n_sup);
+    CW.wsdmin512 = (const double *)take(8 * (size_t)(L + 2));
+    return off - pad + 256 + 64;  // (the alignment comes out of the slack)
+}
+
+// a kernel templated on the kind (0 DEL, 1 DUP) for a run-time kind
+#define CNV_LAUNCH_KIND(kind, kern, grid, block, st, ...)                                  \
+    do {                                                                                   \
+        if ((kind) == 0) hipLaunchKernelGGL(kern<0>, grid, block, 0, st, __VA_ARGS__);     \
+        else hipLaunchKernelGGL(kern<1>, grid, block, 0, st, __VA_ARGS__);                 \
+    } while (0)
+
+// One chromosome's CNV run: what cnv_chrom's phases share.  The phases are
+// member functions, in the order they run; each launches, copies and calls
+// into cnvcall.cpp for the arithmetic.
+struct Chrom {
+    CnvScratch *S;
+    hipStream_t st;
+    const grom_params &P;
+    const char *chr_name, *d_ref;
+    const int64_t len, m, W;
+    int32_t *d_mq;
+    const int32_t *d_rd, *d_low;
+    char *err;
+    size_t errlen;
+    Args A{};
+    int64_t n_blk = 0, n_seg = 0, L = 0, ML = 0;
+    // device pointers
+    uint8_t *gcw = nullptr, *acw = nullptr, *rtype = nullptr, *flag = nullptr;
+    double *sd = nullptr;
+    MiscWords *misc = nullptr;
+    const Tables *dT = nullptr;
+    // host results the later phases read
+    unsigned long long hacc[4] = {0, 0, 0, 0};
+    std::vector<RepeatRec> reps;
+    int biased = -1;
+    std::vector<long> ss, se;  // g_lowvar_block_sample_*_list
+    long half = 0;
+    Tables T{};
+    std::vector<int32_t> flat;  // the bins' samples, back to back (uploaded asynchronously)
+    RepeatSamples RS;
+    std::vector<GatherRange> rrg;  // the biased type's repeats with their flanks
+    std::vector<double> wsd;
+    WalkIn WI{};
+    CandWords CW{};
+    int64_t span = 0, n_ch = 0;
+    std::vector<CallRec> found[2];
+    int64_t n_rows = 0;
+    HostDump dump;
     // GROM_TIMING: per-phase wall clock (syncs the stream at each mark)
     const bool tmg = getenv("GROM_TIMING") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
+    std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
     std::string tlog;
-    auto mark = [&](const char *what) {
+
+    Chrom(CnvScratch *S_, hipStream_t st_, const grom_params &P_, const char *chr_name_, const char *d_ref_, int64_t len_,
+          int32_t *d_mq_, const int32_t *d_rd_, const int32_t *d_low_, char *err_, size_t errlen_)
+        : S(S_), st(st_), P(P_), chr_name(chr_name_), d_ref(d_ref_), len(len_), m(P_.insert_mean),
+          W(2 * (int64_t)P_.insert_mean - 1), d_mq(d_mq_), d_rd(d_rd_), d_low(d_low_), err(err_), errlen(errlen_),
+          dump(chr_name_) {}
+
+    void mark(const char *what) {
         if (!tmg) return;
         (void)hipStreamSynchronize(st);
         auto now = std::chrono::steady_clock::now();
@@ -3571,8 +3313,23 @@ int cnv_chrom(CnvScratch *S, hipStream_t st, const grom_params &P, uint32_t seed
         snprintf(b, sizeof(b), " %s %.2f", what, std::chrono::duration<double, std::milli>(now - t_last).count());
         tlog += b;
         t_last = now;
-    };
-    Args A{};
+    }
+
+    int begin();
+    int gc_windows();
+    int depth_statistics();
+    int sampling(uint32_t seed);
+    int flags_and_z();
+    int side_file(std::string *side);
+    int windows();
+    int repeat_override();
+    int walk_inputs();
+    int searches();
+    int rows_of(std::string &rows);
+};
+
+int Chrom::begin() {
+    int rc;
     A.len = len;
     A.lo = m - 1;
     A.hi = std::max<int64_t>(A.lo, len - W);
@@ -3580,8 +3337,11 @@ int cnv_chrom(CnvScratch *S, hipStream_t st, const grom_params &P, uint32_t seed
     A.ranks_stdev = P.ranks_stdev;
     A.mapq_factor = P.mapq_factor;
     A.dup_factor = (double)P.dup_threshold_factor;
-    const int64_t n_blk = len / BLOCK_UNIT;
-    const int64_t n_seg = (len + SEG_W - 1) / SEG_W;
+    n_blk = len / BLOCK_UNIT;
+    n_seg = (len + SEG_W - 1) / SEG_W;
+    L = P.max_rd_window_len;
+    ML = P.min_rd_window_len;
+    half = m / 2;
     if ((rc = grow(S->gcw, len, err, errlen)) || (rc = grow(S->acw, len, err, errlen)) ||
         (rc = grow(S->rtype, len, err, errlen)) || (rc = grow(S->flag, len, err, errlen)) ||
         (rc = grow(S->sd, 8 * len, err, errlen)) || (rc = grow(S->vis, len, err, errlen)) ||
@@ -3590,19 +3350,21 @@ int cnv_chrom(CnvScratch *S, hipStream_t st, const grom_params &P, uint32_t seed
         (rc = grow(S->hist, 4 * (HIST_MAX + 1), err, errlen)) || (rc = grow(S->tiles, n_seg, err, errlen)) ||
         (rc = grow(S->carry, n_seg, err, errlen)) || (rc = grow(S->ztab, 2 * 2 * NBINS * ZT_MAX, err, errlen)) || (rc = grow(S->tabs, sizeof(Tables), err, errlen)))
         return rc;
-    uint8_t *gcw = (uint8_t *)S->gcw.p, *acw = (uint8_t *)S->acw.p, *rtype = (uint8_t *)S->rtype.p,
-            *flag = (uint8_t *)S->flag.p;
-    double *sd = (double *)S->sd.p;
-    char *misc = (char *)S->misc.p;
-    unsigned long long *acc = (unsigned long long *)misc;  // [0..3] block/chromosome sums
-    uint32_t *n_rep = (uint32_t *)(misc + 64);
-    // misc + 80: candidate count of the window search (n_pre + 1)
+    gcw = (uint8_t *)S->gcw.p, acw = (uint8_t *)S->acw.p, rtype = (uint8_t *)S->rtype.p, flag = (uint8_t *)S->flag.p;
+    sd = (double *)S->sd.p;
+    misc = (MiscWords *)S->misc.p;
+    dT = (const Tables *)S->tabs.p;
     CK(hipEventRecord(S->e0, st));
-    CK(hipMemsetAsync(misc, 0, 128, st));
+    CK(hipMemsetAsync(misc, 0, sizeof(MiscWords), st));
     CK(hipMemsetAsync(S->hist.p, 0, 4 * (HIST_MAX + 1), st));
+    return GROM_OK;
+}
 
-    // ---- A14: weighted GC / ACGT and repeat classes (already running if the
-    // driver prelaunched them for this reference) ----
+// ---- A14: weighted GC / ACGT and repeat classes (already running if the
+// driver prelaunched them for this reference) ----
+int Chrom::gc_windows() {
+    int rc;
+    const int64_t total_w = (int64_t)m * m;  // g_one_base_window_size_total, GROM.c:22265-22269
     if (S->gc_ref == d_ref && S->gc_len == len && S->gc_m == m) {
         CK(hipStreamWaitEvent(st, S->gc_done, 0));
     } else if (m > GC_MMAX || gc_global_forced()) {
@@ -3625,22 +3387,27 @@ int cnv_chrom(CnvScratch *S, hipStream_t st, const grom_params &P, uint32_t seed
         CK(hipGetLastError());
     }
     S->gc_ref = nullptr;
-    // ---- A15: mapq division, blocks, chromosome depth ----
+    return GROM_OK;
+}
+
+// ---- A15: mapq division, blocks, chromosome depth; the most biased repeat
+// and the low-variance sample blocks ----
+int Chrom::depth_statistics() {
+    int rc;
     hipLaunchKernelGGL(k_cnv_blocks, dim3((unsigned)(n_blk + 1)), dim3(256), 0, st, d_ref, A, d_mq, d_rd, d_low, acw,
-                       (int64_t *)S->blk.p, acc, (unsigned int *)S->hist.p);
+                       (int64_t *)S->blk.p, misc->acc, (unsigned int *)S->hist.p);
     CK(hipGetLastError());
     uint32_t rep_cap = (uint32_t)std::min<int64_t>(len / std::max<int64_t>(P.min_repeat, 1) + 1, 1 << 24);
     if ((rc = grow(S->rep, sizeof(RepeatRec) * rep_cap, err, errlen))) return rc;
     if (A.hi > A.lo)
         hipLaunchKernelGGL(k_cnv_repeats, dim3((unsigned)((A.hi - A.lo + 255) / 256)), dim3(256), 0, st, rtype, d_rd,
-                           d_low, A, P.min_repeat, (RepeatRec *)S->rep.p, n_rep, rep_cap);
+                           d_low, A, P.min_repeat, (RepeatRec *)S->rep.p, &misc->n_rep, rep_cap);
     CK(hipGetLastError());
-    unsigned long long hacc[4];
     uint32_t hnrep = 0;
     std::vector<int64_t> blk_total(n_blk + 1);
     std::vector<unsigned int> hist(HIST_MAX + 1);
-    CK(hipMemcpyAsync(hacc, acc, 32, hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(&hnrep, n_rep, 4, hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(hacc, misc->acc, sizeof(hacc), hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(&hnrep, &misc->n_rep, 4, hipMemcpyDeviceToHost, st));
     CK(hipMemcpyAsync(blk_total.data(), S->blk.p, 8 * (n_blk + 1), hipMemcpyDeviceToHost, st));
     CK(hipMemcpyAsync(hist.data(), S->hist.p, 4 * (HIST_MAX + 1), hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
@@ -3648,77 +3415,21 @@ int cnv_chrom(CnvScratch *S, hipStream_t st, const grom_params &P, uint32_t seed
         snprintf(err, errlen, "repeat list overflow (%u > %u)", hnrep, rep_cap);
         return GROM_E_OVERFLOW;
     }
-    std::vector<RepeatRec> reps(hnrep);
+    reps.resize(hnrep);
     if (hnrep) {
         CK(hipMemcpyAsync(reps.data(), S->rep.p, sizeof(RepeatRec) * hnrep, hipMemcpyDeviceToHost, st));
         CK(hipStreamSynchronize(st));
     }
     std::sort(reps.begin(), reps.end(), [](const RepeatRec &a, const RepeatRec &b) { return a.start < b.start; });
+    dump.put("hacc", hacc, sizeof(hacc));
+    dump.vec("hist", hist);
+    dump.vec("blk_total", blk_total);
+    dump.vec("reps", reps);
 
-    // chromosome depth mean over ACGT-rich bases, GROM.c:16645-16660: a double
-    // sum of integers below 2^53, so the exact integer total is the same value
-    double chr_ave = 0;
-    const long chr_cnt = (long)hacc[3];
-    if (chr_cnt > 0) chr_ave = (double)hacc[2] / chr_cnt;
-    // repeat-type depth and the most biased repeat, GROM.c:16686-16775
-    double rave[10] = {0}, rsd[10] = {0};
-    long rcnt[10] = {0};
-    std::vector<double> rrl(reps.size());
-    for (size_t i = 0; i < reps.size(); i++) {
-        rrl[i] = (double)reps[i].rd / (reps[i].end - reps[i].start);
-        rave[reps[i].type] += (rrl[i] < 2 * chr_ave) ? rrl[i] : 2 * chr_ave;
-        rcnt[reps[i].type] += 1;
-    }
-    for (int t = 0; t < 10; t++) rave[t] = rave[t] / (double)rcnt[t];
-    for (size_t i = 0; i < reps.size(); i++) {
-        int t = reps[i].type;
-        double v = (rrl[i] < 2 * chr_ave) ? rrl[i] : 2 * chr_ave;
-        rsd[t] += (v - rave[t]) * (v - rave[t]);
-    }
-    for (int t = 0; t < 10; t++) rsd[t] = rcnt[t] > 1 ? sqrt(rsd[t] / ((double)rcnt[t] - 1.0)) : 0;
-    // The chromosome depth stdev (GROM.c:16664-16685) is a sequential double
-    // sum in base order, and it only feeds the comparison below.  The terms
-    // are the reference's own doubles; only their summation order differs, so
-    // the reference's sum lies within gamma(n) = n*u/(1-n*u) (relative) of the
-    // exact sum of the histogram's terms.  When every comparison comes out the
-    // same at both ends of that interval it is decided; otherwise (or when the
-    // depth histogram cannot hold twice the mean) the sum is redone on the host
-    // in base order.
-    auto biased_for = [&](double sd) {
-        int b = -1;
-        long bc = 0;
-        for (int t = 0; t < 10; t++)
-            if (rcnt[t] > NO_COMBINE && (rave[t] + (P.min_repeat_stdev * rsd[t])) < chr_ave &&
-                (chr_ave - (P.min_repeat_stdev * sd)) > rave[t] && rcnt[t] > bc) {
-                b = t;
-                bc = rcnt[t];
-            }
-        return b;
-    };
-    int biased = -1;
-    bool decided = false;
-    if (chr_cnt <= 1) {
-        biased = biased_for(0.0);
-        decided = true;
-    } else if (!(2 * chr_ave >= HIST_MAX) && !getenv("GROM_CNV_SERIAL_SD")) {
-        long double s = 0;
-        for (int v = 0; v < HIST_MAX; v++) {
-            if (!hist[v]) continue;
-            double term = (v < 2 * chr_ave) ? (v - chr_ave) * (v - chr_ave) : chr_ave * chr_ave;
-            s += (long double)term * hist[v];
-        }
-        s += (long double)hist[HIST_MAX] * (long double)(chr_ave * chr_ave);
-        const long double nu = (long double)chr_cnt * 0x1p-53L;
-        const long double g = nu / (1.0L - nu) + 1e-15L;  // + histogram rounding and sqrt/div ulps
-        const double sd_lo = (double)sqrtl(s * (1.0L - g) / ((long double)chr_cnt - 1.0L));
-        const double sd_hi = (double)sqrtl(s * (1.0L + g) / ((long double)chr_cnt - 1.0L));
-        const int b_lo = biased_for(nextafter(sd_lo, 0.0)), b_hi = biased_for(nextafter(sd_hi, INFINITY));
-        if (b_lo == b_hi) {
-            biased = b_lo;
-            decided = true;
-        }
-    }
-    if (!decided) {
+    const DepthStats D = depth_stats(hacc, reps);
+    // decided from the histogram's bound, else (or GROM_CNV_SERIAL_SD) from the
+    // depth stdev summed in base order on the host
+    if (!((D.chr_cnt <= 1 || !getenv("GROM_CNV_SERIAL_SD")) && biased_repeat_from_hist(D, P, hist, &biased))) {
         const int64_t n = A.hi - A.lo;
         std::vector<int32_t> hrd(n), hlow(n);
         std::vector<uint8_t> hacw(n);
@@ -3726,926 +3437,646 @@ int cnv_chrom(CnvScratch *S, hipStream_t st, const grom_params &P, uint32_t seed
         CK(hipMemcpyAsync(hlow.data(), d_low + A.lo, 4 * n, hipMemcpyDeviceToHost, st));
         CK(hipMemcpyAsync(hacw.data(), acw + A.lo, n, hipMemcpyDeviceToHost, st));
         CK(hipStreamSynchronize(st));
-        double sd = 0;
-        for (int64_t i = 0; i < n; i++) {
-            if (hacw[i] < MIN_ACGT) continue;
-            const int r = hrd[i] + hlow[i];
-            if (r < 2 * chr_ave) sd += (r - chr_ave) * (r - chr_ave);
-            else sd += chr_ave * chr_ave;
-        }
-        sd = sqrt(sd / ((double)chr_cnt - 1.0));
-        biased = biased_for(sd);
+        dump.vec("serial_rd", hrd);
+        dump.vec("serial_low", hlow);
+        dump.vec("serial_acw", hacw);
+        biased = biased_repeat(D, P, depth_sd_serial(D, hrd.data(), hlow.data(), hacw.data(), n));
     }
-    // 10 kb blocks over twice the mean depth -> low-variance sample blocks, GROM.c:16784-16993
-    const double chr_rd_ave = (double)hacc[0] / (double)hacc[1];
-    const double chr_rd_thr = P.chr_rd_threshold_factor * chr_rd_ave;
-    std::vector<long> over;
-    for (int64_t b = 0; b < n_blk; b++)
-        if (blk_total[b] / (double)BLOCK_UNIT > chr_rd_thr) over.push_back((long)b);
-    std::vector<long> bs(MAX_BLOCK_LIST), be(MAX_BLOCK_LIST);
-    long tb = 0, tbs = 0, tbe = 0, nbk = 0;
-    for (size_t a = 1; a < over.size(); a++) {
-        if (tb == 0) {
-            if ((tb + 1) > ((over[a] - over[a - 1]) / BLOCK_FACTOR)) { tbe = over[a] + 1; tb += 1; }
-            else tbe = over[a - 1] + 1;
-            tbs = over[a - 1];
-            tb += 1;
-        } else {
-            if ((tb + 1) > ((over[a - 1] - tbs) / BLOCK_FACTOR)) { tbe = over[a - 1] + 1; tb += 1; }
-            else {
-                if (tb >= P.min_blocks) nbk += 1;
-                tb = 1;
-                tbs = over[a - 1];
-                tbe = over[a - 1] + 1;
-            }
-            if (tb >= P.min_blocks && nbk < MAX_BLOCK_LIST) {
-                bs[nbk] = tbs * BLOCK_UNIT;
-                be[nbk] = tbe * BLOCK_UNIT;
-            }
-        }
-    }
-    if (tb >= P.min_blocks) nbk += 1;
-    std::vector<long> ls(1, 0), le;
-    for (long a = 0; a < nbk && a < MAX_BLOCK_LIST; a++)
-        if (be[a] - bs[a] >= P.block_min) { le.push_back(bs[a]); ls.push_back(be[a]); }
-    le.push_back(len);
-    for (size_t k = 0; k < ls.size(); k++) {
-        for (long *v : {&ls[k], &le[k]}) {
-            if (*v < m - 1) *v = m - 1;
-            else if (*v >= len - W) *v = len - W;
-        }
-    }
-    std::vector<long> ss, se;  // g_lowvar_block_sample_*_list
-    for (size_t k = 0; k < ls.size(); k++)
-        if (!(le[k] - ls[k] < P.min_rd_window_len)) { ss.push_back(ls[k]); se.push_back(le[k]); }
-
+    lowvar_blocks(P, hacc, blk_total, len, ss, se);
+    dump.put("biased", &biased, 4);
+    dump.vec("ss", ss);
+    dump.vec("se", se);
     mark("pre+stats");
-    // ---- A16: GC-bin samples every insert_mean/2 bases, GROM.c:18373-18456 ----
-    const long half = m / 2;
-    const long SAMPLE_LEN = sample_len();  // read per chromosome
-    Tables T{};
-    std::vector<std::vector<int>> smp[2];
-    smp[0].assign(NBINS, {});
-    smp[1].assign(NBINS, {});
-    long idx[2][NBINS] = {{0}}, all[2][NBINS] = {{0}};
-    {
-        std::vector<GatherRange> rg;
-        int64_t tot = 0;
-        for (size_t b = 0; b < ss.size(); b++) {
-            if (se[b] <= ss[b] || half <= 0) continue;
-            int64_t c = (se[b] - ss[b] + half - 1) / half;
-            rg.push_back(GatherRange{ss[b], c, half, tot});
-            tot += c;
-        }
-        Gathered g;
-        if ((rc = gather(S, st, rg, tot, gcw, acw, d_mq, d_rd, d_low, nullptr, g, err, errlen))) return rc;
-        int last_low = 0;
-        long res_over = 0, res_repl = 0;  // reservoir draws past a full list (GROM_CNV_STATS)
-        auto push = [&](int k, int bin, int v) {
-            if (idx[k][bin] < SAMPLE_LEN) {
-                smp[k][bin].push_back(v);
-                idx[k][bin] += 1;
-                all[k][bin] += 1;
-            } else {
-                res_over++;
-                if (rng.grom_rand(all[k][bin]) == 0) { smp[k][bin][rng.grom_rand(idx[k][bin])] = v; res_repl++; }
-                all[k][bin] += 1;
-            }
-        };
-        // (the most-biased-repeat samples come first in the reference and draw
-        // from the same generator, GROM.c:18284-18330)
-        std::vector<std::vector<int>> rsmp(REP_SEGS);
-        long mb_idx[REP_SEGS] = {0}, mb_all[REP_SEGS] = {0};
-        Gathered rgth;
-        std::vector<GatherRange> rrg;
-        if (biased != -1) {
-            int64_t rt_ = 0;
-            for (auto &r : reps)
-                if (r.type == biased) {
-                    rrg.push_back(GatherRange{r.start - half, r.end - r.start + 2 * half, 1, rt_});
-                    rt_ += r.end - r.start + 2 * half;
-                }
-            if ((rc = gather(S, st, rrg, rt_, gcw, acw, d_mq, d_rd, d_low, nullptr, rgth, err, errlen))) return rc;
-            for (auto &x : rrg) {
-                const int64_t rs = x.start + half, re = x.start + x.count - half;
-                for (int64_t i = 0; i < x.count; i++) {
-                    const int64_t pos = x.start + i, o = x.out + i;
-                    if (rgth.ac[o] < MIN_ACGT) continue;
-                    int seg;
-                    if (pos < rs) seg = (int)((REP_SEGS - 1) * (pos - (rs - half)) / half);
-                    else if (pos >= re) seg = (int)((REP_SEGS - 1) * ((re + half) - pos) / half);
-                    else seg = REP_SEGS - 1;
-                    if (mb_idx[seg] < SAMPLE_LEN) {
-                        rsmp[seg].push_back(rgth.rt[o]);
-                        mb_idx[seg]++;
-                        mb_all[seg]++;
-                    } else {
-                        res_over++;
-                        if (rng.grom_rand(mb_all[seg]) == 0) { rsmp[seg][rng.grom_rand(mb_idx[seg])] = rgth.rt[o]; res_repl++; }
-                        mb_all[seg]++;
-                    }
-                }
-            }
-        }
-        for (int64_t i = 0; i < tot; i++) {
-            if (g.ac[i] < MIN_ACGT) continue;
-            const int bin = g.gc[i], v = g.rt[i];
-            if (v == 0) push(last_low, bin, v);
-            else if (g.mq[i] >= P.rd_min_mapq) { push(0, bin, v); last_low = 0; }
-            else { push(1, bin, v); last_low = 1; }
-        }
-        for (int k = 0; k < 2; k++)
-            for (int b = 0; b < NBINS; b++) sort_depths(smp[k][b]);
-        if (const char *sp = getenv("GROM_CNV_STATS")) {
-            FILE *sf = fopen(sp, "a");
-            if (sf) { fprintf(sf, "%s over=%ld repl=%ld\n", chr_name, res_over, res_repl); fclose(sf); }
-        }
-        // thin bins borrow their +-2 neighbours' samples, GROM.c:18480-18548
-        for (int k = 0; k < 2; k++) {
-            std::vector<std::vector<int>> add(NBINS);
-            bool thin[NBINS];
-            for (int b = 0; b < NBINS; b++)
-                thin[b] = b >= 2 && b < NBINS - 2 && idx[k][b] >= RD_MIN_WINDOWS && idx[k][b] < NO_COMBINE;
-            for (int b = 0; b < NBINS; b++) {
-                if (!thin[b]) continue;
-                long n = idx[k][b];
-                for (int a = b - 2; a <= b + 2; a++)
-                    if (a != b)
-                        for (long j = 0; j < idx[k][a] && n < SAMPLE_LEN; j++, n++) add[b].push_back(smp[k][a][j]);
-            }
-            for (int b = 0; b < NBINS; b++)
-                if (thin[b]) {
-                    smp[k][b].insert(smp[k][b].end(), add[b].begin(), add[b].end());
-                    idx[k][b] = (long)smp[k][b].size();
-                    sort_depths(smp[k][b]);
-                }
-        }
-        // repeat-segment statistics, GROM.c:18336-18367 (only with a biased repeat)
-        double rp_ave[REP_SEGS] = {0}, rp_sd[REP_SEGS] = {0};
-        if (biased != -1) {
-            for (int r = 0; r < REP_SEGS; r++) {
-                std::sort(rsmp[r].begin(), rsmp[r].end());
-                if (mb_idx[r] > 0) {
-                    long s0 = mb_idx[r] / 20, e0 = mb_idx[r] - s0, n0 = e0 - s0;
-                    for (long a = s0; a < e0; a++) rp_ave[r] += rsmp[r][a];
-                    rp_ave[r] = rp_ave[r] / n0;
-                    for (long a = s0; a < e0; a++) rp_sd[r] += pow((rsmp[r][a] - rp_ave[r]), 2);
-                    if (n0 > 1) rp_sd[r] = sqrt(rp_sd[r] / (n0 - 1));
-                }
-            }
-        }
-        // bin statistics, GROM.c:18560-18641
-        const double del_f = (1.0 - PLOIDY_NUM / P.ploidy), dup_f = (1.0 + PLOIDY_NUM / P.ploidy);
-        std::vector<int32_t> flat;
-        for (int k = 0; k < 2; k++)
-            for (int b = 0; b < NBINS; b++) {
-                const long n = idx[k][b];
-                const std::vector<int> &l = smp[k][b];
-                T.off[k][b] = (int32_t)flat.size();
-                T.cnt[k][b] = (int32_t)n;
-                flat.insert(flat.end(), l.begin(), l.end());
-                if (n > 0) {
-                    double a = 0.0;
-                    for (long j = 0; j < n; j++) a += l[j];
-                    a = a / n;
-                    // the same sequential sum; pow() evaluated once per run of equal depths
-                    double s = 0.0;
-                    for (long j = 0; j < n;) {
-                        const int v = l[j];
-                        const double term = pow((v - a), 2);
-                        for (; j < n && l[j] == v; j++) s += term;
-                    }
-                    if (n > 1) s = sqrt(s / (n - 1));
-                    T.ave[k][b] = a;
-                    T.sdv[k][b] = s;
-                    T.thr[0][k][b] = del_f * a;
-                    T.thr[1][k][b] = dup_f * a;
-                    T.wins[k][b] = n;
-                }
-            }
-        // pval2sd, find_disc_svs GROM.c:20705-20748
-        {
-            const double pp = 0.3275911, a1 = 0.254829592, a2 = -0.284496736, a3 = 1.421413741, a4 = -1.453152027,
-                         a5 = 1.061405429, sd_max = 10.0;
-            int n = (int)(sd_max / STDEV_STEP + 0.5) + 1;
-            T.n_p2s = n;
-            for (int k = 0; k < n; k++) {
-                double s = sd_max - k * STDEV_STEP;
-                if (s < 0) s = 0;
-                double x = s / sqrt(2.0), t = 1.0 / (1.0 + pp * x);
-                double e = 1.0 - ((a1 * t + a2 * pow(t, 2) + a3 * pow(t, 3) + a4 * pow(t, 4) + a5 * pow(t, 5)) *
-                                  exp(-pow(x, 2)));
-                T.p2s_p[k] = (1.0 - e) / 2.0;
-                T.p2s_sd[k] = s;
-            }
-        }
-        if ((rc = grow(S->samples, 4 * (flat.size() + 1), err, errlen))) return rc;
-        if (!flat.empty())
-            CK(hipMemcpyAsync(S->samples.p, flat.data(), 4 * flat.size(), hipMemcpyHostToDevice, st));
-        CK(hipMemcpyAsync(S->tabs.p, &T, sizeof(Tables), hipMemcpyHostToDevice, st));
-        const Tables *dT = (const Tables *)S->tabs.p;
-
-        mark("sampling");
-        // ---- flags, z scores ----
-        int8_t *tl = (int8_t *)S->tiles.p, *cr = (int8_t *)S->carry.p;
-        const unsigned sblk = (unsigned)((n_seg + 3) / 4);  // 4 waves per block
-        hipLaunchKernelGGL(k_cnv_seg_last<1>, dim3(sblk), dim3(256), 0, st, A, acw, flag, d_mq, d_rd, d_low, tl);
-        hipLaunchKernelGGL(k_cnv_carry, dim3(1), dim3(1024), 0, st, tl, n_seg, cr);
-        hipLaunchKernelGGL(k_cnv_flags, dim3(sblk), dim3(256), 0, st, A, acw, gcw, d_mq, d_rd, d_low, cr, dT, flag);
-        hipLaunchKernelGGL(k_cnv_seg_last<2>, dim3(sblk), dim3(256), 0, st, A, acw, flag, d_mq, d_rd, d_low, tl);
-        hipLaunchKernelGGL(k_cnv_carry, dim3(1), dim3(1024), 0, st, tl, n_seg, cr);
-        if (P.ranks_stdev != 0)
-            hipLaunchKernelGGL(k_cnv_ztab, dim3((2 * NBINS * ZT_MAX + 255) / 256), dim3(256), 0, st, dT,
-                               (const int32_t *)S->samples.p, A.dup_factor, (int16_t *)S->ztab.p);
-        hipLaunchKernelGGL(k_cnv_z, dim3(sblk), dim3(256), 0, st, A, gcw, d_mq, d_rd, d_low, flag, cr, dT,
-                           (const int32_t *)S->samples.p, (const int16_t *)S->ztab.p, sd);
-        CK(hipGetLastError());
-
-        mark("flags+z");
-        // ---- the -N side file (its flags are final here; GROM.c:20234-20345) ----
-        if (side && P.gen1000_window > 0) {
-            const int64_t win = P.gen1000_window, n_win = len / win;
-            side->clear();
-            if (n_win > 0) {
-                if ((rc = grow(S->gen1000, (size_t)n_win * 24, err, errlen))) return rc;
-                double *d_cn = (double *)S->gen1000.p, *d_s2 = d_cn + n_win;
-                int64_t *d_n = (int64_t *)(d_s2 + n_win);
-                hipLaunchKernelGGL(k_cnv_gen1000, dim3((unsigned)((n_win + 255) / 256)), dim3(256), 0, st, flag, d_mq,
-                                   d_rd, d_low, gcw, dT, win, n_win, (int)P.rd_min_mapq, (int)P.ploidy, d_cn, d_s2, d_n);
-                CK(hipGetLastError());
-                std::vector<double> hcn((size_t)n_win), hs2((size_t)n_win);
-                std::vector<int64_t> hn((size_t)n_win);
-                CK(hipMemcpyAsync(hcn.data(), d_cn, 8 * n_win, hipMemcpyDeviceToHost, st));
-                CK(hipMemcpyAsync(hs2.data(), d_s2, 8 * n_win, hipMemcpyDeviceToHost, st));
-                CK(hipMemcpyAsync(hn.data(), d_n, 8 * n_win, hipMemcpyDeviceToHost, st));
-                CK(hipStreamSynchronize(st));
-                side->reserve((size_t)n_win * 40);
-                for (int64_t w = 0; w < n_win; w++) {
-                    const double sd_w = hn[w] > 0 ? sqrt(hs2[w] / (double)hn[w]) : 0.0;
-                    char line[128];
-                    const int nl = snprintf(line, sizeof(line), "%ld\t%e\t%e\n", (long)(w * win), hcn[w], sd_w);
-                    side->append(line, (size_t)nl);
-                }
-            }
-        }
-        // ---- window means by length, GROM.c:18967-19018 ----
-        const int64_t L = P.max_rd_window_len, F = P.windows_sampling_factor, ML = P.min_rd_window_len;
-        std::vector<WinDesc> wds;
-        std::vector<WinPiece> wps;
-        std::vector<int64_t> rlen;
-        long twc = 0;  // ddd_temp_win_count carries across blocks
-        for (size_t b = 0; b < ss.size(); b++) {
-            std::vector<std::pair<int64_t, int64_t>> segs;  // (start, count) of each sampling pass
-            for (int64_t s = 0; s < F; s++) {
-                int64_t a = ss[b] + s * L / F;
-                if (a < se[b]) segs.push_back({a, se[b] - a});
-            }
-            // chop the concatenation into windows of L
-            size_t si = 0;
-            int64_t so = 0;
-            while (si < segs.size()) {
-                WinDesc d{};
-                int64_t need = L, got = 0;
-                d.piece0 = (int64_t)wps.size();
-                while (need > 0 && si < segs.size()) {
-                    int64_t take = std::min(need, segs[si].second - so);
-                    wps.push_back(WinPiece{segs[si].first + so, take});
-                    so += take;
-                    need -= take;
-                    got += take;
-                    if (so == segs[si].second) { si++; so = 0; }
-                }
-                d.n_pieces = (int64_t)wps.size() - d.piece0;
-                d.ntot = got;
-                {
-                    int64_t *pp[3] = {&d.p0, &d.p1, &d.p2}, *nn[3] = {&d.n0, &d.n1, &d.n2};
-                    for (int64_t q = 0; q < 3 && q < d.n_pieces; q++) {
-                        *pp[q] = wps[(size_t)(d.piece0 + q)].start;
-                        *nn[q] = wps[(size_t)(d.piece0 + q)].count;
-                    }
-                }
-                if (twc == 0 && got >= ML) {
-                    d.row = (int64_t)wds.size();
-                    wds.push_back(d);
-                    rlen.push_back(got);
-                } else {
-                    wps.resize((size_t)d.piece0);  // not sampled: its pieces are not needed
-                }
-                if (got == L) { twc += 1; if (twc == REDUCTION) twc = 0; }
-            }
-        }
-        const int64_t n_win = (int64_t)wds.size();
-        if ((rc = grow(S->wd, sizeof(WinDesc) * (n_win + 1) + sizeof(WinPiece) * (wps.size() + 1), err, errlen)) ||
-            (rc = grow(S->rows, 8 * (size_t)std::max<int64_t>(n_win, 1) * (L + 1), err, errlen)) ||
-            (rc = grow(S->rowlen, 8 * (n_win + 1), err, errlen)) || (rc = grow(S->wtot, 8 * (L + 1), err, errlen)) ||
-            (rc = grow(S->wcnt, 8 * (L + 1), err, errlen)) || (rc = grow(S->wsd, 8 * (L + 1), err, errlen)))
-            return rc;
-        std::vector<double> wtot(L + 1, 0.0), wsd(L + 1, 0.0);
-        std::vector<int64_t> wcnt(L + 1, 0);
-        if (n_win > 0) {
-            WinPiece *d_pcs = (WinPiece *)((WinDesc *)S->wd.p + n_win);
-            CK(hipMemcpyAsync(S->wd.p, wds.data(), sizeof(WinDesc) * n_win, hipMemcpyHostToDevice, st));
-            CK(hipMemcpyAsync(d_pcs, wps.data(), sizeof(WinPiece) * wps.size(), hipMemcpyHostToDevice, st));
-            CK(hipMemcpyAsync(S->rowlen.p, rlen.data(), 8 * n_win, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_cnv_windows, dim3((unsigned)((n_win + 63) / 64)), dim3(256), 0, st,
-                               (const WinDesc *)S->wd.p, (const WinPiece *)d_pcs, n_win, flag, sd, L, ML,
-                               (double *)S->rows.p);
-            hipLaunchKernelGGL(k_cnv_window_sq, dim3((unsigned)((L - ML + 1 + 63) / 64)), dim3(256), 0, st,
-                               (const double *)S->rows.p, n_win, (const int64_t *)S->rowlen.p, L, ML,
-                               (double *)S->wtot.p, (int64_t *)S->wcnt.p);
-            CK(hipGetLastError());
-            CK(hipMemcpyAsync(wtot.data(), S->wtot.p, 8 * (L + 1), hipMemcpyDeviceToHost, st));
-            CK(hipMemcpyAsync(wcnt.data(), S->wcnt.p, 8 * (L + 1), hipMemcpyDeviceToHost, st));
-            CK(hipStreamSynchronize(st));
-        }
-        for (int64_t l = ML; l <= L; l++) wsd[l] = wcnt[l] > 1 ? sqrt(wtot[l] / (wcnt[l] - 1)) : 0.0;  // GROM.c:19162
-
-        mark("windows");
-        // ---- most-biased repeat z override, GROM.c:19022-19150 ----
-        if (biased != -1 && !rrg.empty()) {
-            Gathered rg2;
-            int64_t rt_ = rrg.back().out + rrg.back().count;
-            if ((rc = gather(S, st, rrg, rt_, gcw, acw, d_mq, d_rd, d_low, flag, rg2, err, errlen))) return rc;
-            std::vector<double> zv(rt_);
-            std::vector<int64_t> zp(rt_);
-            int64_t nz = 0;
-            for (auto &x : rrg) {
-                const int64_t rs = x.start + half, re = x.start + x.count - half;
-                for (int64_t i = 0; i < x.count; i++) {
-                    const int64_t pos = x.start + i, o = x.out + i;
-                    int seg;
-                    if (pos < rs) seg = (int)((REP_SEGS - 1) * (pos - (rs - half)) / half);
-                    else if (pos >= re) seg = (int)((REP_SEGS - 1) * ((re + half) - pos) / half);
-                    else seg = REP_SEGS - 1;
-                    if (rg2.flag[o] & F_LOW) continue;
-                    const long n = mb_idx[seg];
-                    const int *l = rsmp[seg].data();
-                    const int r = rg2.rt[o];
-                    auto bl = [&](int v) { long s_ = 0, e_ = n; int fd = 0; long i_ = s_ + (e_ - s_) / 2, lo = s_, hi = e_;
-                        while (!fd) { if (i_ <= s_) { i_ = (v <= l[s_]) ? s_ : s_ + 1; fd = 1; } else if (i_ >= e_ - 1) { i_ = (v <= l[e_ - 1]) ? e_ - 1 : e_; fd = 1; }
-                            else if (v <= l[i_]) { hi = i_; i_ = lo + (i_ - lo) / 2; if (hi == i_) { fd = 1; i_ += 1; } }
-                            else { lo = i_; i_ = i_ + (hi - i_) / 2; if (lo == i_) { fd = 1; i_ += 1; } } } return i_; };
-                    auto br = [&](int v) { long s_ = 0, e_ = n; int fd = 0; long i_ = s_ + (e_ - s_) / 2, lo = s_, hi = e_;
-                        while (!fd) { if (i_ <= s_) { i_ = (v < l[s_]) ? s_ : s_ + 1; fd = 1; } else if (i_ >= e_ - 1) { i_ = (v < l[e_ - 1]) ? e_ - 1 : e_; fd = 1; }
-                            else if (v < l[i_]) { hi = i_; i_ = lo + (i_ - lo) / 2; if (hi == i_) { fd = 1; i_ += 1; } }
-                            else { lo = i_; i_ = i_ + (hi - i_) / 2; if (lo == i_) { fd = 1; i_ += 1; } } } return i_; };
-                    auto brd = [&](double v) { long s_ = 0, e_ = T.n_p2s; int fd = 0; long i_ = s_ + (e_ - s_) / 2, lo = s_, hi = e_; const double *q = T.p2s_p;
-                        while (!fd) { if (i_ <= s_) { i_ = (v < q[s_]) ? s_ : s_ + 1; fd = 1; } else if (i_ >= e_ - 1) { i_ = (v < q[e_ - 1]) ? e_ - 1 : e_; fd = 1; }
-                            else if (v < q[i_]) { hi = i_; i_ = lo + (i_ - lo) / 2; if (hi == i_) { fd = 1; i_ += 1; } }
-                            else { lo = i_; i_ = i_ + (hi - i_) / 2; if (lo == i_) { fd = 1; i_ += 1; } } } return i_; };
-                    long i1, i2;
-                    double z;
-                    if (r < rp_ave[seg]) {
-                        i1 = br(r);
-                        i2 = bl(r);
-                        double d1 = (i1 <= 0) ? 0.5 : (double)i1, d2 = (i2 <= 0) ? 0.5 : (double)i2;
-                        i1 = brd((d1 + d2) / (2 * n));
-                        if (i1 < 0) i1 = 0; else if (i1 >= T.n_p2s) i1 = T.n_p2s - 1;
-                        z = P.ranks_stdev == 0 ? (rp_ave[seg] - rg2.rd[o] - rg2.low[o]) / rp_sd[seg] : T.p2s_sd[i1];
-                    } else {
-                        const bool ov = r > A.dup_factor * rp_ave[seg];
-                        if (ov) { i1 = bl((int)(A.dup_factor * rp_ave[seg])); i2 = br(r); }
-                        else { i1 = bl(r); i2 = br(r); }
-                        i1 = n - i1;
-                        i2 = n - i2;
-                        double d1 = (i1 <= 0) ? 0.5 : (double)i1, d2 = (i2 <= 0) ? 0.5 : (double)i2;
-                        i1 = brd((d1 + d2) / (2 * n));
-                        if (i1 < 0) i1 = 0; else if (i1 >= T.n_p2s) i1 = T.n_p2s - 1;
-                        if (P.ranks_stdev == 0)
-                            z = ov ? (A.dup_factor - 1) * (-rp_ave[seg]) / rp_sd[seg]
-                                   : (rp_ave[seg] - rg2.rd[o] - rg2.low[o]) / rp_sd[seg];
-                        else z = -T.p2s_sd[i1];
-                    }
-                    zp[nz] = pos;
-                    zv[nz] = z;
-                    nz++;
-                }
-            }
-            // later writes win, as in the reference's loop order: keep each
-            // position's last value, then one upload and a scatter
-            std::vector<int64_t> ord(nz);
-            for (int64_t i = 0; i < nz; i++) ord[i] = i;
-            std::stable_sort(ord.begin(), ord.end(), [&](int64_t x, int64_t y) { return zp[x] < zp[y]; });
-            std::vector<int64_t> up_p;
-            std::vector<double> up_z;
-            up_p.reserve(nz);
-            up_z.reserve(nz);
-            for (int64_t k = 0; k < nz; k++) {
-                const int64_t i = ord[k];
-                if (k + 1 < nz && zp[ord[k + 1]] == zp[i]) continue;  // a later write to the same base wins
-                up_p.push_back(zp[i]);
-                up_z.push_back(zv[i]);
-            }
-            const int64_t nu = (int64_t)up_p.size();
-            if (nu > 0) {
-                if ((rc = grow(S->zover, 16 * (size_t)nu, err, errlen))) return rc;
-                int64_t *dp = (int64_t *)S->zover.p;
-                double *dz = (double *)(dp + nu);
-                CK(hipMemcpyAsync(dp, up_p.data(), 8 * nu, hipMemcpyHostToDevice, st));
-                CK(hipMemcpyAsync(dz, up_z.data(), 8 * nu, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_cnv_zscatter, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, st, dp, dz, nu, sd);
-                CK(hipGetLastError());
-                CK(hipStreamSynchronize(st));  // the host vectors are released on return
-            }
-        }
-        CK(hipMemcpyAsync(S->wsd.p, wsd.data(), 8 * (L + 1), hipMemcpyHostToDevice, st));
-
-        // ---- DEL then DUP walk over the one lowvar block [m-1, len-W) ----
-        hipLaunchKernelGGL(k_cnv_wbits, dim3((unsigned)std::min<int64_t>((len + 255) / 256, 65536)), dim3(256), 0, st,
-                           A, gcw, d_mq, d_rd, d_low, flag, dT, (uint16_t *)S->wbits.p);
-        CK(hipGetLastError());
-        WalkIn WI{(const uint16_t *)S->wbits.p, sd, (const double *)S->wsd.p, len, m - 1, (len - W) - ML, L, ML,
-                  nullptr};
-        // bit words and block sums for the candidate classification (both kinds)
-        CandWords CW{};
-        {
-            const int64_t n_words = (len + 63) / 64 + 1, n_seg = (n_words + CW_SEG - 1) / CW_SEG;
-            const int64_t n_sup = (n_words + CW_SUP - 1) / CW_SUP;
-            const size_t wbytes = (size_t)n_words * (15 * 8 + 4 * 8 + 8 * 8 + 1) + 256 + 2 * 8 * (size_t)n_words * 64 +
-                                  sizeof(SuperW) * (size_t)n_sup + 8 * (size_t)(L + 2) + 64;
-            if ((rc = grow(S->cwords, wbytes, err, errlen)) || (rc = grow(S->cw_seg, (size_t)n_seg, err, errlen)) ||
-                (rc = grow(S->cw_carry, (size_t)n_seg, err, errlen)) || (rc = grow(S->wsdmin, 8 * (size_t)(L + 2), err, errlen)))
-                return rc;
-            uint64_t *u = (uint64_t *)S->cwords.p;
-            CW.n_words = n_words;
-            CW.nl = u;
-            CW.def = u + n_words;
-            CW.pm = u + 2 * n_words;   // 4 words
-            CW.pk = u + 6 * n_words;   // 2 words
-            CW.defa = u + 8 * n_words;
-            CW.c1a = u + 9 * n_words;
-            CW.c1n = u + 10 * n_words;
-            CW.pa = u + 11 * n_words;  // 4 words
-            double *dd = (double *)(u + 15 * n_words);
-            CW.bsum = dd;
-            CW.bmax = dd + n_words;
-            CW.bmin = dd + 2 * n_words;
-            CW.babs = dd + 3 * n_words;
-            CW.rsn = dd + 4 * n_words;
-            CW.rsa = CW.rsn + n_words * 64;
-            CW.bmax4 = CW.rsa + n_words * 64;
-            CW.bmin4 = CW.bmax4 + 4 * n_words;
-            CW.kend = (int8_t *)(CW.bmin4 + 4 * n_words);
-            {
-                uintptr_t q = ((uintptr_t)(CW.kend + n_words) + 63) & ~(uintptr_t)63;
-                CW.sup = (SuperW *)q;
-                CW.n_sup = n_sup;
-                CW.wsdmin512 = (const double *)(CW.sup + n_sup);
-            }
-            const unsigned gs = (unsigned)((n_seg * 64 + 255) / 256);
-            hipLaunchKernelGGL(k_cnv_cls_seg, dim3(gs), dim3(256), 0, st, (const uint16_t *)S->wbits.p, len, n_seg,
-                               (int8_t *)S->cw_seg.p);
-            hipLaunchKernelGGL(k_cnv_carry, dim3(1), dim3(1024), 0, st, (const int8_t *)S->cw_seg.p, n_seg,
-                               (int8_t *)S->cw_carry.p);
-            hipLaunchKernelGGL(k_cnv_words, dim3(gs), dim3(256), 0, st, (const uint16_t *)S->wbits.p, (const double *)sd,
-                               len, n_seg, (const int8_t *)S->cw_carry.p, CW);
-            CK(hipGetLastError());
-            std::vector<double> wmin((size_t)L + 2, 0.0);
-            for (int64_t a = 0; a <= L; a++) {
-                double v = wsd[a];
-                for (int64_t b2 = a + 1; b2 <= std::min<int64_t>(a + 63, L); b2++) v = std::min(v, wsd[b2]);
-                wmin[a] = v;
-            }
-            wmin[L + 1] = 0.0;
-            CK(hipMemcpyAsync(S->wsdmin.p, wmin.data(), 8 * (L + 2), hipMemcpyHostToDevice, st));
-            // the same over 512 lengths (phase B's block skip), from the 64-length minima
-            std::vector<double> wmin512((size_t)L + 2, 0.0);
-            for (int64_t a = 0; a <= L; a++) {
-                double v = wmin[a];
-                for (int64_t b2 = a + 64; b2 <= std::min<int64_t>(a + 511, L); b2 += 64) v = std::min(v, wmin[b2]);
-                wmin512[a] = v;
-            }
-            CK(hipMemcpyAsync((void *)CW.wsdmin512, wmin512.data(), 8 * (L + 2), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_cnv_super, dim3((unsigned)((n_sup + 255) / 256)), dim3(256), 0, st, CW);
-            CK(hipGetLastError());
-            CK(hipStreamSynchronize(st));  // wmin is released on scope exit
-        }
-        const int64_t span = std::max<int64_t>(0, WI.end - WI.start);
-        const int64_t n_ch = (span + WALK_CHUNK - 1) / WALK_CHUNK;
-        uint32_t call_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(4096, len / 1000), 1 << 24);
-        uint32_t pre_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(1 << 16, len / 64), 1 << 26);
-        uint32_t cand_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(1 << 16, len / 4), (int64_t)1 << 30);
-        std::vector<CallRec> found[2];
-        // both threads call this one lambda: the buffer caps are per-call locals
-        auto run_kind = [&, call_cap0 = call_cap, pre_cap0 = pre_cap, cand_cap0 = cand_cap](int kind, char *err,
-                                                                                          size_t errlen) -> int {
-            uint32_t call_cap = call_cap0, pre_cap = pre_cap0, cand_cap = cand_cap0;
-            KindBufs &K = S->kb[kind];
-            hipStream_t st = K.st;
-            int rc = GROM_OK;
-            if ((rc = grow(K.cnt, 512, err, errlen)) || (rc = grow(K.vis, (size_t)len, err, errlen))) return rc;
-            // n_calls, n_pre, n_cand, capped, n_und; walk counters from byte 64
-            uint32_t *n_calls = (uint32_t *)K.cnt.p, *n_pre = n_calls + 1;
-            WalkIn WK = WI;
-            WK.t_defa = CW.defa;
-            WK.t_c1a = CW.c1a;
-            WK.t_defn = CW.def;
-            WK.t_c1n = CW.c1n;
-            WK.t_nl = CW.nl;
-            WK.t_pa0 = CW.pa + (kind * 2 + 0) * CW.n_words;
-            WK.t_pa1 = CW.pa + (kind * 2 + 1) * CW.n_words;
-            WK.t_pn0 = CW.pm + (kind * 2 + 0) * CW.n_words;
-            WK.t_pn1 = CW.pm + (kind * 2 + 1) * CW.n_words;
-            WK.stats = tmg ? (unsigned long long *)((char *)K.cnt.p + 64) : nullptr;
-            WK.prof = tmg ? WK.stats + 40 : nullptr;  // slots 40..48 (the mode offsets reach slot 21)
-            CK(hipStreamWaitEvent(st, S->walk_in, 0));
-            if (WK.stats) CK(hipMemsetAsync(WK.stats, 0, 448, st));
-            bool done = false;
-            for (int attempt = 0; attempt < 8 && !done; attempt++) {
-                if ((rc = grow(K.nxt, 8 * (size_t)len, err, errlen)) ||
-                    (rc = grow(K.pre, sizeof(PreAB) * pre_cap, err, errlen)) ||
-                    (rc = grow(K.prepos, 8 * (size_t)cand_cap, err, errlen)) ||
-                    (rc = grow(K.ppos, 8 * (size_t)pre_cap, err, errlen)) ||
-                    (rc = grow(K.calls, sizeof(CallRec) * call_cap, err, errlen)) ||
-                    (rc = grow(K.ok, call_cap, err, errlen)) ||
-                    (rc = grow(K.tiles, sizeof(ChunkState) * n_ch, err, errlen)) ||
-                    (rc = grow(K.pend, sizeof(SlideState) * n_ch, err, errlen)) ||
-                    (rc = grow(K.plist, 4 * (size_t)n_ch, err, errlen)))
-                    return rc;
-                ChunkState *dcs = (ChunkState *)K.tiles.p;
-                CallRec *dcalls = (CallRec *)K.calls.p;
-                uint8_t *vis = (uint8_t *)K.vis.p;
-                // the kind's counters in one fill: n_calls, n_pre, n_cand, the
-                // capped call starts, n_und, the queue head (n_calls[0..5])
-                CK(hipMemsetAsync(n_calls, 0, 24, st));
-                CK(hipMemsetAsync(vis, 0, len, st));
-                int32_t *nxt = (int32_t *)K.nxt.p;
-                PreAB *pre = (PreAB *)K.pre.p;
-                const unsigned gpre = (unsigned)((span + 255) / 256);
-                uint32_t *n_cand = n_pre + 1;
-                int64_t *cand = (int64_t *)K.prepos.p;
-                if (kind == 0)
-                    hipLaunchKernelGGL(k_cnv_cand<0>, dim3(gpre), dim3(256), 0, st, WK, nxt, cand, n_cand, cand_cap);
-                else
-                    hipLaunchKernelGGL(k_cnv_cand<1>, dim3(gpre), dim3(256), 0, st, WK, nxt, cand, n_cand, cand_cap);
-                CK(hipGetLastError());
-                uint32_t ncand = 0;
-                CK(hipMemcpyAsync(&ncand, n_cand, 4, hipMemcpyDeviceToHost, st));
-                CK(hipStreamSynchronize(st));
-                if (ncand > cand_cap) {
-                    cand_cap = ncand + ncand / 4 + 1024;
-                    found[kind].clear();
-                    continue;
-                }
-                if (ncand) {
-                    // GROM_CNV_BUDGET (tests) shrinks the precompute budgets so the
-                    // walk's wave routines take the long searches; GROM_CNV_CLASSIFY=0
-                    // sends every candidate through the exact per-lane phases A/B
-                    const char *bud = getenv("GROM_CNV_BUDGET");
-                    const int64_t budget = bud ? std::max<int64_t>(atoll(bud), 1) : (int64_t)1 << 27;
-                    const char *cl = getenv("GROM_CNV_CLASSIFY");
-                    const bool classify = !(cl && strcmp(cl, "0") == 0);
-                    // candidates whose phases A/B are computed exactly, one lane each
-                    const int64_t *pcand = cand;
-                    uint32_t npc = ncand;
-                    if (classify) {
-                        // no-ops and phase-A jumps settled here; the undecided rest listed
-                        if ((rc = grow(K.und, 8 * (size_t)ncand, err, errlen))) return rc;
-                        int64_t *und = (int64_t *)K.und.p;
-                        uint32_t *n_und = n_pre + 3;
-                        uint32_t *qhead = n_pre + 4;  // the classification's work queue
-                        // a fixed grid of waves pulling candidates (k_cnv_classify): enough
-                        // to fill the chip, never more than the candidates need
-                        const unsigned gcls = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ncand + 255) / 256, 2048));
-                        static const int cls_queue = [] {
-                            // default: lane per candidate (150 Mb chromosome, walks
-                            // 32-34 ms against 40-41 ms with the queue)
-                            const char *e = getenv("GROM_CNV_CLS");
-                            return e ? atoi(e) : 0;
-                        }();
-                        if (!cls_queue) {
-                            const unsigned gl = (unsigned)((ncand + 255) / 256);
-                            if (kind == 0)
-                                hipLaunchKernelGGL(k_cnv_classify_lane<0>, dim3(gl), dim3(256), 0, st, WK, cand, ncand, CW, (const double *)S->wsdmin.p, nxt, und, n_und, ncand);
-                            else
-                                hipLaunchKernelGGL(k_cnv_classify_lane<1>, dim3(gl), dim3(256), 0, st, WK, cand, ncand, CW, (const double *)S->wsdmin.p, nxt, und, n_und, ncand);
-                        } else if (kind == 0)
-                            hipLaunchKernelGGL(k_cnv_classify<0>, dim3(gcls), dim3(256), 0, st, WK, cand, ncand, CW, (const double *)S->wsdmin.p, nxt, und, n_und, ncand, qhead);
-                        else
-                            hipLaunchKernelGGL(k_cnv_classify<1>, dim3(gcls), dim3(256), 0, st, WK, cand, ncand, CW, (const double *)S->wsdmin.p, nxt, und, n_und, ncand, qhead);
-                        CK(hipGetLastError());
-                        uint32_t nu = 0;
-                        CK(hipMemcpyAsync(&nu, n_und, 4, hipMemcpyDeviceToHost, st));
-                        CK(hipStreamSynchronize(st));
-                        // few undecided (calls in the noise): exact per-lane precompute;
-                        // many (calls inside long regions, of which the walk visits the
-                        // first): the walk decides them
-                        npc = (int64_t)nu * L <= budget ? nu : 0;
-                        pcand = und;
-                        if (tmg) {
-                            unsigned long long cs8[8];
-                            (void)hipMemcpy(cs8, WK.stats + 24, sizeof(cs8), hipMemcpyDeviceToHost);
-                            unsigned long long cb4[4];
-                            (void)hipMemcpy(cb4, WK.stats + 32, sizeof(cb4), hipMemcpyDeviceToHost);
-                            fprintf(stderr, "cnv classify %s blocks: %llu reached, %llu with known pass bits, %llu walk clear, %llu skipped\n",
-                                    kind == 0 ? "DEL" : "DUP", cb4[0], cb4[1], cb4[2], cb4[3]);
-                            fprintf(stderr, "cnv classify %s: %u candidates, %u undecided (%s); jumps %llu, first-window "
-                                    "undecided %llu, B undecided %llu, no-ops %llu, bases tested %llu, segments settled by the bound %llu, "
-                                    "segments tested %llu\n", kind == 0 ? "DEL" : "DUP", ncand, nu,
-                                    npc ? "precomputed" : "left to the walk", cs8[1], cs8[2], cs8[5], cs8[6], cs8[3],
-                                    cs8[4], cs8[7]);
-                        }
-                    }
-                    if (npc > pre_cap) {  // every precomputed candidate may start a call: no re-run
-                        pre_cap = npc;
-                        if ((rc = grow(K.pre, sizeof(PreAB) * pre_cap, err, errlen)) ||
-                            (rc = grow(K.ppos, 8 * (size_t)pre_cap, err, errlen)))
-                            return rc;
-                        pre = (PreAB *)K.pre.p;
-                    }
-                    if (npc) {
-                        const int64_t ab_cap = bud ? std::max<int64_t>(std::min<int64_t>(L, budget / npc), ML + 256) : L;
-                        if (kind == 0)
-                            hipLaunchKernelGGL(k_cnv_pre<0>, dim3((npc + 255) / 256), dim3(256), 0, st, WK, pcand, npc, nxt, pre, n_pre, pre_cap, (int64_t *)K.ppos.p, ab_cap);
-                        else
-                            hipLaunchKernelGGL(k_cnv_pre<1>, dim3((npc + 255) / 256), dim3(256), 0, st, WK, pcand, npc, nxt, pre, n_pre, pre_cap, (int64_t *)K.ppos.p, ab_cap);
-                        CK(hipGetLastError());
-                        // phases C/D for every call start, within the same kind of budget
-                        // (the walk finishes the rest)
-                        const int64_t cd_cap = std::max<int64_t>(
-                            std::min<int64_t>(4 * L + 4 * MAX_DIST_LAST_GOOD, budget / std::max<uint32_t>(npc / 4, 1)),
-                            (int64_t)1024);
-                        const unsigned gpost = (unsigned)((std::min<int64_t>(npc, pre_cap) + 255) / 256);
-                        if (kind == 0)
-                            hipLaunchKernelGGL(k_cnv_post<0>, dim3(gpost), dim3(256), 0, st, WK, pre, n_pre, pre_cap, (const int64_t *)K.ppos.p, cd_cap, n_pre + 2);
-                        else
-                            hipLaunchKernelGGL(k_cnv_post<1>, dim3(gpost), dim3(256), 0, st, WK, pre, n_pre, pre_cap, (const int64_t *)K.ppos.p, cd_cap, n_pre + 2);
-                        CK(hipGetLastError());
-                    }
-                }
-                const unsigned gch = (unsigned)n_ch;  // one wave per chunk
-                SlideState *pend = (SlideState *)K.pend.p;
-                if (kind == 0)
-                    hipLaunchKernelGGL(k_cnv_walk<0>, dim3(gch), dim3(64), 0, st, WK, nxt, pre, 0, n_ch, WALK_CHUNK, vis, dcs, pend, dcalls, n_calls, call_cap);
-                else
-                    hipLaunchKernelGGL(k_cnv_walk<1>, dim3(gch), dim3(64), 0, st, WK, nxt, pre, 0, n_ch, WALK_CHUNK, vis, dcs, pend, dcalls, n_calls, call_cap);
-                CK(hipGetLastError());
-                std::vector<ChunkState> hcs(n_ch);
-                // paused slides (k_cnv_walk_resume): resume, round by round, the
-                // pending chunks whose predecessor's exit is known and lands in
-                // them; a pending chunk that exit jumps over takes that exit
-                std::vector<int32_t> plist;
-                int n_rounds = 0;
-                for (;;) {
-                    CK(hipMemcpyAsync(hcs.data(), dcs, sizeof(ChunkState) * n_ch, hipMemcpyDeviceToHost, st));
-                    CK(hipStreamSynchronize(st));
-                    plist.clear();
-                    bool covered = false;
-                    for (int64_t k = 0; k < n_ch; k++) {
-                        if (hcs[k].status != ST_PENDING) continue;
-                        if (k > 0 && hcs[k - 1].status == ST_PENDING) continue;
-                        const int64_t c1 = std::min<int64_t>(WK.end, WK.start + (k + 1) * WALK_CHUNK);
-                        if (k > 0 && hcs[k - 1].x1 >= c1) {
-                            hcs[k].x1 = hcs[k - 1].x1;
-                            hcs[k].l1 = hcs[k - 1].l1;
-                            hcs[k].status = ST_MERGED;
-                            covered = true;
-                        } else {
-                            plist.push_back((int32_t)k);
-                        }
-                    }
-                    if (covered) CK(hipMemcpyAsync(dcs, hcs.data(), sizeof(ChunkState) * n_ch, hipMemcpyHostToDevice, st));
-                    if (plist.empty()) break;
-                    n_rounds++;
-                    CK(hipMemcpyAsync(K.plist.p, plist.data(), 4 * plist.size(), hipMemcpyHostToDevice, st));
-                    const int32_t *dl = (const int32_t *)K.plist.p;
-                    if (kind == 0)
-                        hipLaunchKernelGGL(k_cnv_walk_resume<0>, dim3((unsigned)plist.size()), dim3(64), 0, st, WK, nxt, pre, dl, WALK_CHUNK, vis, dcs, pend, dcalls, n_calls, call_cap);
-                    else
-                        hipLaunchKernelGGL(k_cnv_walk_resume<1>, dim3((unsigned)plist.size()), dim3(64), 0, st, WK, nxt, pre, dl, WALK_CHUNK, vis, dcs, pend, dcalls, n_calls, call_cap);
-                    CK(hipGetLastError());
-                }
-                if (tmg) fprintf(stderr, "cnv walk %s: %d resume rounds\n", kind == 0 ? "DEL" : "DUP", n_rounds);
-                if (kind == 0)
-                    hipLaunchKernelGGL(k_cnv_walk<0>, dim3(gch), dim3(64), 0, st, WK, nxt, pre, 1, n_ch, WALK_CHUNK, vis, dcs, pend, dcalls, n_calls, call_cap);
-                else
-                    hipLaunchKernelGGL(k_cnv_walk<1>, dim3(gch), dim3(64), 0, st, WK, nxt, pre, 1, n_ch, WALK_CHUNK, vis, dcs, pend, dcalls, n_calls, call_cap);
-                CK(hipGetLastError());
-                // reconcile (k_cnv_reconcile, one wave): the true exit of each
-                // chunk in order, repairs, the chunks the walk jumps over
-                if ((rc = grow(K.skip, (size_t)n_ch, err, errlen))) return rc;
-                uint32_t *d_nfix = n_calls + 8;  // (a free word of the counters, byte 32)
-                if (kind == 0)
-                    hipLaunchKernelGGL(k_cnv_reconcile<0>, dim3(1), dim3(64), 0, st, WK, nxt, pre, n_ch, WALK_CHUNK, vis, dcs,
-                                       dcalls, n_calls, call_cap, (uint8_t *)K.skip.p, d_nfix);
-                else
-                    hipLaunchKernelGGL(k_cnv_reconcile<1>, dim3(1), dim3(64), 0, st, WK, nxt, pre, n_ch, WALK_CHUNK, vis, dcs,
-                                       dcalls, n_calls, call_cap, (uint8_t *)K.skip.p, d_nfix);
-                CK(hipGetLastError());
-                int64_t n_fix = 0;
-                if (tmg) {
-                    uint32_t np_[3] = {0, 0, 0};
-                    (void)hipMemcpy(np_, n_pre, 12, hipMemcpyDeviceToHost);
-                    unsigned long long wsa[22] = {0};
-                    (void)hipMemcpy(wsa, WK.stats, sizeof(wsa), hipMemcpyDeviceToHost);
-                    for (int mo = 0; mo < 4; mo++)
-                        fprintf(stderr, "cnv walk %s %s: stops %llu, wave A/B %llu, wave C/D %llu, slide rounds %llu, trim rounds %llu\n",
-                                kind == 0 ? "DEL" : "DUP", mo == 0 ? "mode 0" : mo == 1 ? "mode 1" : mo == 2 ? "repairs" : "resumed",
-                                wsa[5 * mo + 4], wsa[5 * mo], wsa[5 * mo + 1], wsa[5 * mo + 2], wsa[5 * mo + 3]);
-                    fprintf(stderr, "cnv walk %s: longest resumed slide %llu steps in %llu wall-clock ticks\n",
-                            kind == 0 ? "DEL" : "DUP", wsa[20], wsa[21]);
-                    unsigned long long ck2[9];
-                    (void)hipMemcpy(ck2, WK.stats + 40, sizeof(ck2), hipMemcpyDeviceToHost);
-                    fprintf(stderr, "cnv walk %s: slide cycles %llu: before the sum chain %llu, chain %llu, after %llu; "
-                            "longest resumed slide %llu clocks; chain guesses repaired %llu; longest resumed wave %llu "
-                            "clocks (trim %llu, walk on %llu)\n",
-                            kind == 0 ? "DEL" : "DUP", ck2[1], ck2[2], ck2[0], ck2[3], ck2[4], ck2[5], ck2[6], ck2[7],
-                            ck2[8]);
-                    unsigned long long ws[5];
-                    for (int q = 0; q < 5; q++) ws[q] = wsa[q] + wsa[5 + q] + wsa[10 + q] + wsa[15 + q];
-                    fprintf(stderr, "cnv walk %s: %lld chunks, %lld repaired, %u candidates, %u call starts (%u left to the walk); "
-                            "walk stops %llu, wave A/B %llu, wave C/D %llu (%llu slide rounds, %llu trim rounds)\n",
-                            kind == 0 ? "DEL" : "DUP", (long long)n_ch, (long long)n_fix, ncand, np_[0], np_[2], ws[4],
-                            ws[0], ws[1], ws[2], ws[3]);
-                }
-                // n_calls, n_pre (adjacent) and the repairs in one copy
-                uint32_t hn[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-                CK(hipMemcpyAsync(hn, n_calls, sizeof(hn), hipMemcpyDeviceToHost, st));
-                CK(hipStreamSynchronize(st));
-                const uint32_t nc = hn[0], npre = hn[1];
-                n_fix = hn[8];
-                (void)n_fix;
-                if (npre > pre_cap || nc > call_cap) {
-                    pre_cap = std::max(pre_cap, npre + npre / 4 + 1024);
-                    call_cap = std::max(call_cap, nc + nc / 4 + 1024);
-                    found[kind].clear();
-                    continue;
-                }
-                std::vector<CallRec> hc(nc);
-                std::vector<uint8_t> ok(nc);
-                if (nc) {
-                    hipLaunchKernelGGL(k_cnv_calls_valid, dim3((nc + 255) / 256), dim3(256), 0, st, dcalls, nc, vis,
-                                       (const uint8_t *)K.skip.p, WK.start, WALK_CHUNK, (uint8_t *)K.ok.p);
-                    CK(hipMemcpyAsync(hc.data(), dcalls, sizeof(CallRec) * nc, hipMemcpyDeviceToHost, st));
-                    CK(hipMemcpyAsync(ok.data(), K.ok.p, nc, hipMemcpyDeviceToHost, st));
-                    CK(hipStreamSynchronize(st));
-                }
-                for (uint32_t i = 0; i < nc; i++)
-                    if (ok[i]) found[kind].push_back(hc[i]);
-                std::sort(found[kind].begin(), found[kind].end(),
-                          [](const CallRec &a, const CallRec &b) { return a.p < b.p; });
-                found[kind].erase(std::unique(found[kind].begin(), found[kind].end(),
-                                              [](const CallRec &a, const CallRec &b) { return a.p == b.p; }),
-                                  found[kind].end());
-                done = true;
-            }
-            if (!done) {
-                snprintf(err, errlen, "CNV window-search buffers could not be sized");
-                return GROM_E_NOMEM;
-            }
-            return GROM_OK;
-        };
-        if (n_ch > 0) {
-            CK(hipEventRecord(S->walk_in, st));
-            char kerr[2][512] = {{0}, {0}};
-            int krc[2] = {GROM_OK, GROM_OK};
-            int dev = 0;
-            CK(hipGetDevice(&dev));
-            std::thread dup_thread([&] {  // a new host thread starts on device 0: select ours
-                if (hipSetDevice(dev) != hipSuccess) {
-                    snprintf(kerr[1], sizeof(kerr[1]), "hipSetDevice(%d) failed in the CNV DUP thread", dev);
-                    krc[1] = GROM_E_HIP;
-                    return;
-                }
-                krc[1] = run_kind(1, kerr[1], sizeof(kerr[1]));
-            });
-            krc[0] = run_kind(0, kerr[0], sizeof(kerr[0]));
-            dup_thread.join();
-            for (int kind = 0; kind < 2; kind++)
-                if (krc[kind] != GROM_OK) {
-                    snprintf(err, errlen, "%s", kerr[kind]);
-                    return krc[kind];
-                }
-        }
-        CK(hipEventRecord(S->e1, st));
-        mark("walks");
-
-        // ---- p value (Q8), filter, copy number, rows: GROM.c:17139-17300, 20024-20228 ----
-        const double pp = 0.3275911, a1 = 0.254829592, a2 = -0.284496736, a3 = 1.421413741, a4 = -1.453152027,
-                     a5 = 1.061405429;
-        int64_t n_rows = 0;
-        for (int kind = 0; kind < 2; kind++) {
-            std::vector<std::pair<size_t, double>> keep;
-            for (size_t i = 0; i < found[kind].size(); i++) {
-                double x = fabs(found[kind][i].stdevs) / sqrt(2.0);
-                double t = 1.0 / (1.0 + pp + x);
-                double e = 1.0 - ((a1 * t + a2 * pow(t, 2) + a3 * pow(t, 3) + a4 * pow(t, 4) + a5 * pow(t, 5)) *
-                                  exp(-pow(x, 2)));
-                double pv = (1.0 - e) / 2.0;
-                if (pv < P.rd_pval_threshold) keep.push_back({i, pv});
-            }
-            std::vector<GatherRange> rg;
-            int64_t tot = 0;
-            for (auto &kp : keep) {
-                const CallRec &c = found[kind][kp.first];
-                int64_t n = std::max<int64_t>(0, c.ce - c.p);
-                rg.push_back(GatherRange{c.p, n, 1, tot});
-                tot += n;
-            }
-            const auto tg0 = std::chrono::steady_clock::now();
-            if (tot > 0) {
-                const size_t nb = (size_t)tot;
-                if ((rc = grow(S->gat_rg, sizeof(GatherRange) * rg.size(), err, errlen)) ||
-                    (rc = grow(S->cn_v, 8 * nb, err, errlen)))
-                    return rc;
-                if (S->h_cn_cap < nb) {
-                    if (S->h_cn) (void)hipHostFree(S->h_cn);
-                    S->h_cn = nullptr;
-                    S->h_cn_cap = 0;
-                    const size_t want = nb + nb / 4 + 4096;
-                    CK(hipHostMalloc((void **)&S->h_cn, 8 * want, 0));
-                    S->h_cn_cap = want;
-                }
-                CK(hipMemcpyAsync(S->gat_rg.p, rg.data(), sizeof(GatherRange) * rg.size(), hipMemcpyHostToDevice, st));
-                const int g_ = (int)std::min<int64_t>((tot + 255) / 256, 16384);
-                hipLaunchKernelGGL(k_cnv_cn_ratio, dim3(g_), dim3(256), 0, st, (const GatherRange *)S->gat_rg.p,
-                                   (int)rg.size(), gcw, d_mq, d_rd, d_low, flag, dT, (int32_t)P.rd_min_mapq, tot,
-                                   (double *)S->cn_v.p);
-                CK(hipGetLastError());
-                CK(hipMemcpyAsync(S->h_cn, S->cn_v.p, 8 * nb, hipMemcpyDeviceToHost, st));
-                CK(hipStreamSynchronize(st));
-            }
-            const auto tg1 = std::chrono::steady_clock::now();
-            // copy number of every kept call (GROM.c:20100-20160): independent per
-            // call, so host threads share them; the rows are then written in order
-            std::vector<double> cnv_cn(keep.size(), -1.0), cnv_cs(keep.size(), 0.0);
-            auto cn_of = [&](size_t j, std::vector<double> &pl, std::vector<double> &tmp) {
-                pl.clear();
-                const double *v = S->h_cn + rg[j].out;
-                for (int64_t i = 0; i < rg[j].count; i++)
-                    if (v[i] < HUGE_VAL) pl.push_back(v[i]);  // (the reference's list, in base order)
-                double cn = -1, cns = 0;
-                const long pc = (long)pl.size();
-                if (pc > 0) {
-                    tmp.resize(pc);
-                    msort_lo_par(pl.data(), pl.size(), tmp.data(), 3);
-                    long s0 = 0.1 * pc, e0 = pc - s0;
-                    double sum = 0.0;
-                    for (long i = s0; i < e0; i++) sum += pl[i];
-                    if (e0 - s0 > 0) {
-                        cn = (sum / (e0 - s0)) * P.ploidy;
-                        cns = 0;
-                        for (long i = 0; i < pc; i++) cns += pow((P.ploidy * pl[i] - cn), 2);
-                        cns = sqrt(cns / pc);
-                    }
-                }
-                cnv_cn[j] = cn;
-                cnv_cs[j] = cns;
-            };
-            {
-                int64_t work = 0;
-                for (size_t j = 0; j < keep.size(); j++) work += rg[j].count;
-                const unsigned nt = (unsigned)std::min<int64_t>({(int64_t)8, (int64_t)keep.size(), 1 + work / 200000});
-                std::atomic<size_t> next{0};
-                auto worker = [&] {
-                    std::vector<double> pl, tmp;
-                    for (size_t j; (j = next.fetch_add(1)) < keep.size();) cn_of(j, pl, tmp);
-                };
-                std::vector<std::thread> th;
-                for (unsigned t = 1; t < nt; t++) th.emplace_back(worker);
-                worker();
-                for (auto &t : th) t.join();
-                if (tmg) {
-                    const auto tg2 = std::chrono::steady_clock::now();
-                    int64_t mx = 0;
-                    for (size_t j = 0; j < keep.size(); j++) mx = std::max<int64_t>(mx, rg[j].count);
-                    fprintf(stderr, "cnv rows %s: %zu calls, %lld bases (largest %lld), %u threads; gather %.1f ms, copy number %.1f ms\n",
-                            kind == 0 ? "DEL" : "DUP", keep.size(), (long long)tot, (long long)mx, nt,
-                            std::chrono::duration<double, std::milli>(tg1 - tg0).count(),
-                            std::chrono::duration<double, std::milli>(tg2 - tg1).count());
-                }
-            }
-            // -f: a column header before each kind's rows (GROM.c:17242-17245,
-            // 17378), rows named by caf_del_text / caf_dup_text (GROM.c:1575)
-            if (P.vcf != 1) rows += "SV Type\tChromosome\tStart\tEnd\tStdev from mean\tP Value\tCopy Number\n";
-            for (size_t j = 0; j < keep.size(); j++) {
-                const CallRec &c = found[kind][keep[j].first];
-                char line[512];
-                int nl;
-                if (P.vcf != 1)  // GROM.c:17340-17343
-                    nl = snprintf(line, sizeof(line), "%s\t%s\t%lld\t%lld\t%e\t%e\t%e\t%e\n", kind == 0 ? "DEL RD" : "DUP RD",
-                                  chr_name, (long long)c.p, (long long)c.ce, c.stdevs, keep[j].second, cnv_cn[j], cnv_cs[j]);
-                else
-                    nl = snprintf(line, sizeof(line), "%s\t%lld\t.\t.\t%s\t.\t.\tEND=%lld\tSD:Z:CN:CS\t%e:%e:%.2f:%e\n",
-                                  chr_name, (long long)c.p + 1, kind == 0 ? "<DEL>" : "<DUP>", (long long)c.ce + 1,
-                                  c.stdevs, keep[j].second, cnv_cn[j], cnv_cs[j]);
-                rows.append(line, (size_t)nl);
-                n_rows++;
-            }
-        }
-        mark("rows");
-        if (tmg) fprintf(stderr, "cnv phases ms:%s\n", tlog.c_str());
-        if (timing) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, S->e0, S->e1);
-            timing->ms_device = ms;
-            timing->del_calls = (int64_t)found[0].size();
-            timing->dup_calls = (int64_t)found[1].size();
-            timing->rows = n_rows;
-        }
-    }
-    if (timing)
-        timing->ms_host =
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
     return GROM_OK;
 }
+
+// ---- A16: GC-bin samples every insert_mean/2 bases and the biased repeat
+// type's flank samples -> bin statistics, GROM.c:18284-18641 ----
+int Chrom::sampling(uint32_t seed) {
+    int rc;
+    const long SAMPLE_LEN = sample_len();  // read per chromosome
+    dump.put("seed", &seed, 4);
+    dump.put("sample_len", &SAMPLE_LEN, 8);
+    Reservoir res(seed, SAMPLE_LEN);
+    BinSamples BS;
+    int64_t tot = 0, rtot = 0;
+    const std::vector<GatherRange> rg = bin_sample_ranges(ss, se, half, &tot);
+    Gathered g, rgth;
+    if ((rc = gather(S, st, rg, tot, gcw, acw, d_mq, d_rd, d_low, nullptr, g, err, errlen))) return rc;
+    rrg = repeat_ranges(reps, biased, half, &rtot);
+    if (biased != -1) {
+        if ((rc = gather(S, st, rrg, rtot, gcw, acw, d_mq, d_rd, d_low, nullptr, rgth, err, errlen))) return rc;
+        dump.put("r_ac", rgth.ac, (size_t)rtot);
+        dump.put("r_rt", rgth.rt, 4 * (size_t)rtot);
+        sample_repeats(res, rrg, half, rgth, RS);
+    }
+    dump.put("g_ac", g.ac, (size_t)tot);
+    dump.put("g_gc", g.gc, (size_t)tot);
+    dump.put("g_rt", g.rt, 4 * (size_t)tot);
+    dump.put("g_mq", g.mq, 4 * (size_t)tot);
+    sample_bins(res, tot, g, (int)P.rd_min_mapq, BS);
+    if (const char *sp = getenv("GROM_CNV_STATS")) {
+        FILE *sf = fopen(sp, "a");
+        if (sf) { fprintf(sf, "%s over=%ld repl=%ld\n", chr_name, res.over, res.repl); fclose(sf); }
+    }
+    const long draws[2] = {res.over, res.repl};
+    dump.put("draws", draws, sizeof(draws));
+    borrow_thin_bins(BS, SAMPLE_LEN);
+    if (biased != -1) repeat_segment_stats(RS);
+    bin_stats(BS, P, T, flat);
+    pval2sd_table(T);
+    dump.put("tables", &T, TABLES_BYTES);
+    dump.vec("samples", flat);
+    if ((rc = grow(S->samples, 4 * (flat.size() + 1), err, errlen))) return rc;
+    if (!flat.empty())
+        CK(hipMemcpyAsync(S->samples.p, flat.data(), 4 * flat.size(), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(S->tabs.p, &T, sizeof(Tables), hipMemcpyHostToDevice, st));
+    mark("sampling");
+    return GROM_OK;
+}
+
+// ---- flags, z scores ----
+int Chrom::flags_and_z() {
+    int8_t *tl = (int8_t *)S->tiles.p, *cr = (int8_t *)S->carry.p;
+    const unsigned sblk = (unsigned)((n_seg + 3) / 4);  // 4 waves per block
+    hipLaunchKernelGGL(k_cnv_seg_last<1>, dim3(sblk), dim3(256), 0, st, A, acw, flag, d_mq, d_rd, d_low, tl);
+    hipLaunchKernelGGL(k_cnv_carry, dim3(1), dim3(1024), 0, st, tl, n_seg, cr);
+    hipLaunchKernelGGL(k_cnv_flags, dim3(sblk), dim3(256), 0, st, A, acw, gcw, d_mq, d_rd, d_low, cr, dT, flag);
+    hipLaunchKernelGGL(k_cnv_seg_last<2>, dim3(sblk), dim3(256), 0, st, A, acw, flag, d_mq, d_rd, d_low, tl);
+    hipLaunchKernelGGL(k_cnv_carry, dim3(1), dim3(1024), 0, st, tl, n_seg, cr);
+    if (P.ranks_stdev != 0)
+        hipLaunchKernelGGL(k_cnv_ztab, dim3((2 * NBINS * ZT_MAX + 255) / 256), dim3(256), 0, st, dT,
+                           (const int32_t *)S->samples.p, A.dup_factor, (int16_t *)S->ztab.p);
+    hipLaunchKernelGGL(k_cnv_z, dim3(sblk), dim3(256), 0, st, A, gcw, d_mq, d_rd, d_low, flag, cr, dT,
+                       (const int32_t *)S->samples.p, (const int16_t *)S->ztab.p, sd);
+    CK(hipGetLastError());
+    mark("flags+z");
+    return GROM_OK;
+}
+
+// ---- the -N side file (its flags are final here; GROM.c:20234-20345) ----
+int Chrom::side_file(std::string *side) {
+    int rc;
+    if (!(side && P.gen1000_window > 0)) return GROM_OK;
+    const int64_t win = P.gen1000_window, n_win = len / win;
+    side->clear();
+    if (n_win <= 0) return GROM_OK;
+    if ((rc = grow(S->gen1000, (size_t)n_win * 24, err, errlen))) return rc;
+    double *d_cn = (double *)S->gen1000.p, *d_s2 = d_cn + n_win;
+    int64_t *d_n = (int64_t *)(d_s2 + n_win);
+    hipLaunchKernelGGL(k_cnv_gen1000, dim3((unsigned)((n_win + 255) / 256)), dim3(256), 0, st, flag, d_mq,
+                       d_rd, d_low, gcw, dT, win, n_win, (int)P.rd_min_mapq, (int)P.ploidy, d_cn, d_s2, d_n);
+    CK(hipGetLastError());
+    std::vector<double> hcn((size_t)n_win), hs2((size_t)n_win);
+    std::vector<int64_t> hn((size_t)n_win);
+    CK(hipMemcpyAsync(hcn.data(), d_cn, 8 * n_win, hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(hs2.data(), d_s2, 8 * n_win, hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(hn.data(), d_n, 8 * n_win, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    side->reserve((size_t)n_win * 40);
+    for (int64_t w = 0; w < n_win; w++) {
+        const double sd_w = hn[w] > 0 ? sqrt(hs2[w] / (double)hn[w]) : 0.0;
+        char line[128];
+        const int nl = snprintf(line, sizeof(line), "%ld\t%e\t%e\n", (long)(w * win), hcn[w], sd_w);
+        side->append(line, (size_t)nl);
+    }
+    return GROM_OK;
+}
+
+// ---- window means by length, GROM.c:18967-19018 ----
+int Chrom::windows() {
+    int rc;
+    const WindowPlan WP = window_plan(ss, se, P);
+    dump.vec("wds", WP.wds);
+    dump.vec("wps", WP.wps);
+    dump.vec("rlen", WP.rlen);
+    const int64_t n_win = (int64_t)WP.wds.size();
+    if ((rc = grow(S->wd, sizeof(WinDesc) * (n_win + 1) + sizeof(WinPiece) * (WP.wps.size() + 1), err, errlen)) ||
+        (rc = grow(S->rows, 8 * (size_t)std::max<int64_t>(n_win, 1) * (L + 1), err, errlen)) ||
+        (rc = grow(S->rowlen, 8 * (n_win + 1), err, errlen)) || (rc = grow(S->wtot, 8 * (L + 1), err, errlen)) ||
+        (rc = grow(S->wcnt, 8 * (L + 1), err, errlen)) || (rc = grow(S->wsd, 8 * (L + 1), err, errlen)))
+        return rc;
+    std::vector<double> wtot(L + 1, 0.0);
+    std::vector<int64_t> wcnt(L + 1, 0);
+    if (n_win > 0) {
+        WinPiece *d_pcs = (WinPiece *)((WinDesc *)S->wd.p + n_win);
+        CK(hipMemcpyAsync(S->wd.p, WP.wds.data(), sizeof(WinDesc) * n_win, hipMemcpyHostToDevice, st));
+        CK(hipMemcpyAsync(d_pcs, WP.wps.data(), sizeof(WinPiece) * WP.wps.size(), hipMemcpyHostToDevice, st));
+        CK(hipMemcpyAsync(S->rowlen.p, WP.rlen.data(), 8 * n_win, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_cnv_windows, dim3((unsigned)((n_win + 63) / 64)), dim3(256), 0, st,
+                           (const WinDesc *)S->wd.p, (const WinPiece *)d_pcs, n_win, flag, sd, L, ML,
+                           (double *)S->rows.p);
+        hipLaunchKernelGGL(k_cnv_window_sq, dim3((unsigned)((L - ML + 1 + 63) / 64)), dim3(256), 0, st,
+                           (const double *)S->rows.p, n_win, (const int64_t *)S->rowlen.p, L, ML,
+                           (double *)S->wtot.p, (int64_t *)S->wcnt.p);
+        CK(hipGetLastError());
+        CK(hipMemcpyAsync(wtot.data(), S->wtot.p, 8 * (L + 1), hipMemcpyDeviceToHost, st));
+        CK(hipMemcpyAsync(wcnt.data(), S->wcnt.p, 8 * (L + 1), hipMemcpyDeviceToHost, st));
+        CK(hipStreamSynchronize(st));
+    }
+    dump.vec("wtot", wtot);
+    dump.vec("wcnt", wcnt);
+    wsd = window_sd(wtot, wcnt, ML, L);
+    dump.vec("wsd", wsd);
+    mark("windows");
+    return GROM_OK;
+}
+
+// ---- most-biased repeat z override, GROM.c:19022-19150: one upload and a scatter ----
+int Chrom::repeat_override() {
+    int rc;
+    if (biased != -1 && !rrg.empty()) {
+        Gathered rg2;
+        const int64_t rt_ = rrg.back().out + rrg.back().count;
+        if ((rc = gather(S, st, rrg, rt_, gcw, acw, d_mq, d_rd, d_low, flag, rg2, err, errlen))) return rc;
+        dump.put("o_flag", rg2.flag, (size_t)rt_);
+        dump.put("o_rt", rg2.rt, 4 * (size_t)rt_);
+        dump.put("o_rd", rg2.rd, 4 * (size_t)rt_);
+        dump.put("o_low", rg2.low, 4 * (size_t)rt_);
+        std::vector<int64_t> up_p;
+        std::vector<double> up_z;
+        repeat_z_override(rrg, half, rg2, RS, T, P, A.dup_factor, up_p, up_z);
+        dump.vec("zover_pos", up_p);
+        dump.vec("zover_z", up_z);
+        const int64_t nu = (int64_t)up_p.size();
+        if (nu > 0) {
+            if ((rc = grow(S->zover, 16 * (size_t)nu, err, errlen))) return rc;
+            int64_t *dp = (int64_t *)S->zover.p;
+            double *dz = (double *)(dp + nu);
+            CK(hipMemcpyAsync(dp, up_p.data(), 8 * nu, hipMemcpyHostToDevice, st));
+            CK(hipMemcpyAsync(dz, up_z.data(), 8 * nu, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_cnv_zscatter, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, st, dp, dz, nu, sd);
+            CK(hipGetLastError());
+            CK(hipStreamSynchronize(st));  // the host vectors are released on return
+        }
+    }
+    CK(hipMemcpyAsync(S->wsd.p, wsd.data(), 8 * (L + 1), hipMemcpyHostToDevice, st));
+    return GROM_OK;
+}
+
+// ---- the walk's inputs over the one lowvar block [m-1, len-W): the
+// per-base bit words, and the bit words and block sums of the candidate
+// classification (both kinds) ----
+int Chrom::walk_inputs() {
+    int rc;
+    hipLaunchKernelGGL(k_cnv_wbits, dim3((unsigned)std::min<int64_t>((len + 255) / 256, 65536)), dim3(256), 0, st,
+                       A, gcw, d_mq, d_rd, d_low, flag, dT, (uint16_t *)S->wbits.p);
+    CK(hipGetLastError());
+    WI = WalkIn{(const uint16_t *)S->wbits.p, sd, (const double *)S->wsd.p, len, m - 1, (len - W) - ML, L, ML,
+                nullptr};
+    const int64_t n_words = (len + 63) / 64 + 1, n_wseg = (n_words + CW_SEG - 1) / CW_SEG;
+    const int64_t n_sup = (n_words + CW_SUP - 1) / CW_SUP;
+    if ((rc = grow(S->cwords, carve_cand_words(CW, nullptr, n_words, n_sup, L), err, errlen)) ||
+        (rc = grow(S->cw_seg, (size_t)n_wseg, err, errlen)) || (rc = grow(S->cw_carry, (size_t)n_wseg, err, errlen)) ||
+        (rc = grow(S->wsdmin, 8 * (size_t)(L + 2), err, errlen)))
+        return rc;
+    carve_cand_words(CW, (char *)S->cwords.p, n_words, n_sup, L);
+    const unsigned gs = (unsigned)((n_wseg * 64 + 255) / 256);
+    hipLaunchKernelGGL(k_cnv_cls_seg, dim3(gs), dim3(256), 0, st, (const uint16_t *)S->wbits.p, len, n_wseg,
+                       (int8_t *)S->cw_seg.p);
+    hipLaunchKernelGGL(k_cnv_carry, dim3(1), dim3(1024), 0, st, (const int8_t *)S->cw_seg.p, n_wseg,
+                       (int8_t *)S->cw_carry.p);
+    hipLaunchKernelGGL(k_cnv_words, dim3(gs), dim3(256), 0, st, (const uint16_t *)S->wbits.p, (const double *)sd,
+                       len, n_wseg, (const int8_t *)S->cw_carry.p, CW);
+    CK(hipGetLastError());
+    std::vector<double> wmin, wmin512;
+    window_sd_minima(wsd, L, wmin, wmin512);
+    dump.vec("wmin", wmin);
+    dump.vec("wmin512", wmin512);
+    CK(hipMemcpyAsync(S->wsdmin.p, wmin.data(), 8 * (L + 2), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync((void *)CW.wsdmin512, wmin512.data(), 8 * (L + 2), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_cnv_super, dim3((unsigned)((n_sup + 255) / 256)), dim3(256), 0, st, CW);
+    CK(hipGetLastError());
+    CK(hipStreamSynchronize(st));  // the minima are released on return
+    span = std::max<int64_t>(0, WI.end - WI.start);
+    n_ch = (span + WALK_CHUNK - 1) / WALK_CHUNK;
+    return GROM_OK;
+}
+
+// One kind's (0 DEL, 1 DUP) window search on the kind's own stream, driven by
+// its own host thread: the steps of one attempt are member functions, run()
+// holds the loop that re-runs an attempt whose buffers were too small.
+struct KindRun {
+    Chrom &C;
+    const int kind;
+    KindBufs &K;
+    const hipStream_t st;
+    char *err;
+    size_t errlen;
+    CnvScratch *const S = C.S;
+    const int64_t len = C.len, L = C.L, ML = C.ML, span = C.span, n_ch = C.n_ch;
+    const bool tmg = C.tmg;
+    const char *const name = kind == 0 ? "DEL" : "DUP";
+    uint32_t call_cap, pre_cap, cand_cap;
+    WalkIn WK{};
+    // the kind's device blocks
+    KindCounters *cnt = nullptr;
+    ChunkState *dcs = nullptr;
+    CallRec *dcalls = nullptr;
+    uint8_t *vis = nullptr;
+    int32_t *nxt = nullptr;
+    PreAB *pre = nullptr;
+    int64_t *cand = nullptr;
+    SlideState *pend = nullptr;
+    std::vector<ChunkState> hcs;  // the chunks' states on the host (written back asynchronously)
+    uint32_t ncand = 0;
+    // candidates whose phases A/B are computed exactly, one lane each
+    const int64_t *pcand = nullptr;
+    uint32_t npc = 0;
+    // GROM_CNV_BUDGET (tests) shrinks the precompute budgets so the walk's
+    // wave routines take the long searches
+    const char *const bud = getenv("GROM_CNV_BUDGET");
+    const int64_t budget = bud ? std::max<int64_t>(atoll(bud), 1) : (int64_t)1 << 27;
+
+    KindRun(Chrom &C_, int kind_, char *err_, size_t errlen_)
+        : C(C_), kind(kind_), K(C_.S->kb[kind_]), st(K.st), err(err_), errlen(errlen_) {
+        call_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(4096, len / 1000), 1 << 24);
+        pre_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(1 << 16, len / 64), 1 << 26);
+        cand_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(1 << 16, len / 4), (int64_t)1 << 30);
+    }
+
+    int run();
+    int begin();
+    int size_attempt();
+    int candidates();
+    int classify();
+    int precompute();
+    int walk();
+    int resume_rounds();
+    int reconcile();
+    int collect(bool *retry);
+};
+
+int KindRun::begin() {
+    int rc;
+    if ((rc = grow(K.cnt, sizeof(KindCounters), err, errlen)) || (rc = grow(K.vis, (size_t)len, err, errlen))) return rc;
+    cnt = (KindCounters *)K.cnt.p;
+    const CandWords &CW = C.CW;
+    WK = C.WI;
+    WK.t_defa = CW.defa;
+    WK.t_c1a = CW.c1a;
+    WK.t_defn = CW.def;
+    WK.t_c1n = CW.c1n;
+    WK.t_nl = CW.nl;
+    WK.t_pa0 = CW.pa + (kind * 2 + 0) * CW.n_words;
+    WK.t_pa1 = CW.pa + (kind * 2 + 1) * CW.n_words;
+    WK.t_pn0 = CW.pm + (kind * 2 + 0) * CW.n_words;
+    WK.t_pn1 = CW.pm + (kind * 2 + 1) * CW.n_words;
+    WK.stats = tmg ? (unsigned long long *)&cnt->stats : nullptr;
+    WK.prof = tmg ? cnt->stats.prof : nullptr;
+    CK(hipStreamWaitEvent(st, S->walk_in, 0));
+    if (WK.stats) CK(hipMemsetAsync(WK.stats, 0, sizeof(WalkStats), st));
+    return GROM_OK;
+}
+
+int KindRun::size_attempt() {
+    int rc;
+    if ((rc = grow(K.nxt, 8 * (size_t)len, err, errlen)) ||
+        (rc = grow(K.pre, sizeof(PreAB) * pre_cap, err, errlen)) ||
+        (rc = grow(K.prepos, 8 * (size_t)cand_cap, err, errlen)) ||
+        (rc = grow(K.ppos, 8 * (size_t)pre_cap, err, errlen)) ||
+        (rc = grow(K.calls, sizeof(CallRec) * call_cap, err, errlen)) ||
+        (rc = grow(K.ok, call_cap, err, errlen)) ||
+        (rc = grow(K.tiles, sizeof(ChunkState) * n_ch, err, errlen)) ||
+        (rc = grow(K.pend, sizeof(SlideState) * n_ch, err, errlen)) ||
+        (rc = grow(K.plist, 4 * (size_t)n_ch, err, errlen)))
+        return rc;
+    dcs = (ChunkState *)K.tiles.p;
+    dcalls = (CallRec *)K.calls.p;
+    vis = (uint8_t *)K.vis.p;
+    nxt = (int32_t *)K.nxt.p;
+    pre = (PreAB *)K.pre.p;
+    cand = (int64_t *)K.prepos.p;
+    pend = (SlideState *)K.pend.p;
+    // the kind's counters in one fill
+    CK(hipMemsetAsync(cnt, 0, offsetof(KindCounters, unused), st));
+    CK(hipMemsetAsync(vis, 0, len, st));
+    return GROM_OK;
+}
+
+int KindRun::candidates() {
+    const unsigned gpre = (unsigned)((span + 255) / 256);
+    CNV_LAUNCH_KIND(kind, k_cnv_cand, dim3(gpre), dim3(256), st, WK, nxt, cand, &cnt->n_cand, cand_cap);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(&ncand, &cnt->n_cand, 4, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    return GROM_OK;
+}
+
+// no-ops and phase-A jumps settled here; the undecided rest listed
+int KindRun::classify() {
+    int rc;
+    if ((rc = grow(K.und, 8 * (size_t)ncand, err, errlen))) return rc;
+    int64_t *und = (int64_t *)K.und.p;
+    const unsigned gl = (unsigned)((ncand + 255) / 256);
+    CNV_LAUNCH_KIND(kind, k_cnv_classify_lane, dim3(gl), dim3(256), st, WK, cand, ncand, C.CW,
+                    (const double *)S->wsdmin.p, nxt, und, &cnt->n_und, ncand);
+    CK(hipGetLastError());
+    uint32_t nu = 0;
+    CK(hipMemcpyAsync(&nu, &cnt->n_und, 4, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    // few undecided (calls in the noise): exact per-lane precompute;
+    // many (calls inside long regions, of which the walk visits the
+    // first): the walk decides them
+    npc = (int64_t)nu * L <= budget ? nu : 0;
+    pcand = und;
+    if (tmg) {
+        unsigned long long cs8[8];
+        (void)hipMemcpy(cs8, cnt->stats.classify, sizeof(cs8), hipMemcpyDeviceToHost);
+        unsigned long long cb4[4];
+        (void)hipMemcpy(cb4, cnt->stats.cls_blocks, sizeof(cb4), hipMemcpyDeviceToHost);
+        fprintf(stderr, "cnv classify %s blocks: %llu reached, %llu with known pass bits, %llu walk clear, %llu skipped\n",
+                name, cb4[0], cb4[1], cb4[2], cb4[3]);
+        fprintf(stderr, "cnv classify %s: %u candidates, %u undecided (%s); jumps %llu, first-window "
+                "undecided %llu, B undecided %llu, no-ops %llu, bases tested %llu, segments settled by the bound %llu, "
+                "segments tested %llu\n", name, ncand, nu,
+                npc ? "precomputed" : "left to the walk", cs8[1], cs8[2], cs8[5], cs8[6], cs8[3],
+                cs8[4], cs8[7]);
+    }
+    return GROM_OK;
+}
+
+// phases A/B of the undecided candidates, C/D of every call start they give
+int KindRun::precompute() {
+    int rc;
+    if (npc > pre_cap) {  // every precomputed candidate may start a call: no re-run
+        pre_cap = npc;
+        if ((rc = grow(K.pre, sizeof(PreAB) * pre_cap, err, errlen)) ||
+            (rc = grow(K.ppos, 8 * (size_t)pre_cap, err, errlen)))
+            return rc;
+        pre = (PreAB *)K.pre.p;
+    }
+    if (!npc) return GROM_OK;
+    const int64_t ab_cap = bud ? std::max<int64_t>(std::min<int64_t>(L, budget / npc), ML + 256) : L;
+    CNV_LAUNCH_KIND(kind, k_cnv_pre, dim3((npc + 255) / 256), dim3(256), st, WK, pcand, npc, nxt, pre, &cnt->n_pre,
+                    pre_cap, (int64_t *)K.ppos.p, ab_cap);
+    CK(hipGetLastError());
+    // phases C/D for every call start, within the same kind of budget
+    // (the walk finishes the rest)
+    const int64_t cd_cap = std::max<int64_t>(
+        std::min<int64_t>(4 * L + 4 * MAX_DIST_LAST_GOOD, budget / std::max<uint32_t>(npc / 4, 1)),
+        (int64_t)1024);
+    const unsigned gpost = (unsigned)((std::min<int64_t>(npc, pre_cap) + 255) / 256);
+    CNV_LAUNCH_KIND(kind, k_cnv_post, dim3(gpost), dim3(256), st, WK, pre, &cnt->n_pre, pre_cap,
+                    (const int64_t *)K.ppos.p, cd_cap, &cnt->n_capped);
+    CK(hipGetLastError());
+    return GROM_OK;
+}
+
+int KindRun::walk() {
+    const unsigned gch = (unsigned)n_ch;  // one wave per chunk
+    CNV_LAUNCH_KIND(kind, k_cnv_walk, dim3(gch), dim3(64), st, WK, nxt, pre, 0, n_ch, WALK_CHUNK, vis, dcs, pend, dcalls,
+                    &cnt->n_calls, call_cap);
+    CK(hipGetLastError());
+    return GROM_OK;
+}
+
+// paused slides (k_cnv_walk_resume): resume, round by round, the pending
+// chunks whose predecessor's exit is known and lands in them; a pending chunk
+// that exit jumps over takes that exit.  Then the second walk pass.
+int KindRun::resume_rounds() {
+    hcs.resize(n_ch);
+    std::vector<int32_t> plist;
+    int n_rounds = 0;
+    for (;;) {
+        CK(hipMemcpyAsync(hcs.data(), dcs, sizeof(ChunkState) * n_ch, hipMemcpyDeviceToHost, st));
+        CK(hipStreamSynchronize(st));
+        plist.clear();
+        bool covered = false;
+        for (int64_t k = 0; k < n_ch; k++) {
+            if (hcs[k].status != ST_PENDING) continue;
+            if (k > 0 && hcs[k - 1].status == ST_PENDING) continue;
+            const int64_t c1 = std::min<int64_t>(WK.end, WK.start + (k + 1) * WALK_CHUNK);
+            if (k > 0 && hcs[k - 1].x1 >= c1) {
+                hcs[k].x1 = hcs[k - 1].x1;
+                hcs[k].l1 = hcs[k - 1].l1;
+                hcs[k].status = ST_MERGED;
+                covered = true;
+            } else {
+                plist.push_back((int32_t)k);
+            }
+        }
+        if (covered) CK(hipMemcpyAsync(dcs, hcs.data(), sizeof(ChunkState) * n_ch, hipMemcpyHostToDevice, st));
+        if (plist.empty()) break;
+        n_rounds++;
+        CK(hipMemcpyAsync(K.plist.p, plist.data(), 4 * plist.size(), hipMemcpyHostToDevice, st));
+        const int32_t *dl = (const int32_t *)K.plist.p;
+        CNV_LAUNCH_KIND(kind, k_cnv_walk_resume, dim3((unsigned)plist.size()), dim3(64), st, WK, nxt, pre, dl, WALK_CHUNK,
+                        vis, dcs, pend, dcalls, &cnt->n_calls, call_cap);
+        CK(hipGetLastError());
+    }
+    if (tmg) fprintf(stderr, "cnv walk %s: %d resume rounds\n", name, n_rounds);
+    CNV_LAUNCH_KIND(kind, k_cnv_walk, dim3((unsigned)n_ch), dim3(64), st, WK, nxt, pre, 1, n_ch, WALK_CHUNK, vis, dcs, pend,
+                    dcalls, &cnt->n_calls, call_cap);
+    CK(hipGetLastError());
+    return GROM_OK;
+}
+
+// reconcile (k_cnv_reconcile, one wave): the true exit of each chunk in
+// order, repairs, the chunks the walk jumps over
+int KindRun::reconcile() {
+    int rc;
+    if ((rc = grow(K.skip, (size_t)n_ch, err, errlen))) return rc;
+    CNV_LAUNCH_KIND(kind, k_cnv_reconcile, dim3(1), dim3(64), st, WK, nxt, pre, n_ch, WALK_CHUNK, vis, dcs, dcalls,
+                    &cnt->n_calls, call_cap, (uint8_t *)K.skip.p, &cnt->n_fix);
+    CK(hipGetLastError());
+    if (tmg) {
+        KindCounters hk{};
+        (void)hipMemcpy(&hk, cnt, sizeof(KindCounters), hipMemcpyDeviceToHost);
+        const WalkStats &ws_ = hk.stats;
+        static const char *const mode_name[4] = {"mode 0", "mode 1", "repairs", "resumed"};
+        for (int mo = 0; mo < 4; mo++)
+            fprintf(stderr, "cnv walk %s %s: stops %llu, wave A/B %llu, wave C/D %llu, slide rounds %llu, trim rounds %llu\n",
+                    name, mode_name[mo], ws_.mode[mo][4], ws_.mode[mo][0], ws_.mode[mo][1], ws_.mode[mo][2],
+                    ws_.mode[mo][3]);
+        fprintf(stderr, "cnv walk %s: longest resumed slide %llu steps in %llu wall-clock ticks\n", name,
+                ws_.longest[0], ws_.longest[1]);
+        const unsigned long long *ck2 = ws_.prof;
+        fprintf(stderr, "cnv walk %s: slide cycles %llu: before the sum chain %llu, chain %llu, after %llu; "
+                "longest resumed slide %llu clocks; chain guesses repaired %llu; longest resumed wave %llu "
+                "clocks (trim %llu, walk on %llu)\n",
+                name, ck2[1], ck2[2], ck2[0], ck2[3], ck2[4], ck2[5], ck2[6], ck2[7], ck2[8]);
+        unsigned long long ws[5];
+        for (int q = 0; q < 5; q++) ws[q] = ws_.mode[0][q] + ws_.mode[1][q] + ws_.mode[2][q] + ws_.mode[3][q];
+        fprintf(stderr, "cnv walk %s: %lld chunks, %u repaired, %u candidates, %u call starts (%u left to the walk); "
+                "walk stops %llu, wave A/B %llu, wave C/D %llu (%llu slide rounds, %llu trim rounds)\n",
+                name, (long long)n_ch, hk.n_fix, ncand, hk.n_pre, hk.n_capped, ws[4], ws[0], ws[1], ws[2], ws[3]);
+    }
+    return GROM_OK;
+}
+
+// the valid calls, sorted by start, each start once; *retry when a list overflowed
+int KindRun::collect(bool *retry) {
+    std::vector<CallRec> &found = C.found[kind];
+    KindCounters hk{};  // the counters up to the repairs in one copy
+    CK(hipMemcpyAsync(&hk, cnt, offsetof(KindCounters, unused2), hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    const uint32_t nc = hk.n_calls, npre = hk.n_pre;
+    if (npre > pre_cap || nc > call_cap) {
+        pre_cap = std::max(pre_cap, npre + npre / 4 + 1024);
+        call_cap = std::max(call_cap, nc + nc / 4 + 1024);
+        *retry = true;
+        return GROM_OK;
+    }
+    std::vector<CallRec> hc(nc);
+    std::vector<uint8_t> ok(nc);
+    if (nc) {
+        hipLaunchKernelGGL(k_cnv_calls_valid, dim3((nc + 255) / 256), dim3(256), 0, st, dcalls, nc, vis,
+                           (const uint8_t *)K.skip.p, WK.start, WALK_CHUNK, (uint8_t *)K.ok.p);
+        CK(hipMemcpyAsync(hc.data(), dcalls, sizeof(CallRec) * nc, hipMemcpyDeviceToHost, st));
+        CK(hipMemcpyAsync(ok.data(), K.ok.p, nc, hipMemcpyDeviceToHost, st));
+        CK(hipStreamSynchronize(st));
+    }
+    for (uint32_t i = 0; i < nc; i++)
+        if (ok[i]) found.push_back(hc[i]);
+    std::sort(found.begin(), found.end(), [](const CallRec &a, const CallRec &b) { return a.p < b.p; });
+    found.erase(std::unique(found.begin(), found.end(), [](const CallRec &a, const CallRec &b) { return a.p == b.p; }),
+                found.end());
+    return GROM_OK;
+}
+
+int KindRun::run() {
+    int rc;
+    if ((rc = begin())) return rc;
+    for (int attempt = 0; attempt < 8; attempt++) {
+        C.found[kind].clear();
+        if ((rc = size_attempt()) || (rc = candidates())) return rc;
+        if (ncand > cand_cap) {
+            cand_cap = ncand + ncand / 4 + 1024;
+            continue;
+        }
+        pcand = cand;
+        npc = ncand;
+        if (ncand && ((rc = classify()) || (rc = precompute()))) return rc;
+        bool retry = false;
+        if ((rc = walk()) || (rc = resume_rounds()) || (rc = reconcile()) || (rc = collect(&retry))) return rc;
+        if (!retry) return GROM_OK;
+    }
+    snprintf(err, errlen, "CNV window-search buffers could not be sized");
+    return GROM_E_NOMEM;
+}
+
+// ---- DEL and DUP searches, each on its own stream and host thread ----
+int Chrom::searches() {
+    if (n_ch > 0) {
+        CK(hipEventRecord(S->walk_in, st));
+        char kerr[2][512] = {{0}, {0}};
+        int krc[2] = {GROM_OK, GROM_OK};
+        int dev = 0;
+        CK(hipGetDevice(&dev));
+        KindRun del(*this, 0, kerr[0], sizeof(kerr[0])), dup(*this, 1, kerr[1], sizeof(kerr[1]));
+        std::thread dup_thread([&] {  // a new host thread starts on device 0: select ours
+            if (hipSetDevice(dev) != hipSuccess) {
+                snprintf(kerr[1], sizeof(kerr[1]), "hipSetDevice(%d) failed in the CNV DUP thread", dev);
+                krc[1] = GROM_E_HIP;
+                return;
+            }
+            krc[1] = dup.run();
+        });
+        krc[0] = del.run();
+        dup_thread.join();
+        for (int kind = 0; kind < 2; kind++)
+            if (krc[kind] != GROM_OK) {
+                snprintf(err, errlen, "%s", kerr[kind]);
+                return krc[kind];
+            }
+    }
+    CK(hipEventRecord(S->e1, st));
+    mark("walks");
+    return GROM_OK;
+}
+
+// ---- p value (Q8), filter, copy number, rows: GROM.c:17139-17300, 20024-20228 ----
+int Chrom::rows_of(std::string &rows) {
+    int rc;
+    const size_t rows0 = rows.size();
+    for (int kind = 0; kind < 2; kind++) {
+        const std::vector<KeptCall> keep = keep_calls(found[kind], P.rd_pval_threshold);
+        int64_t tot = 0;
+        const std::vector<GatherRange> rg = call_ranges(found[kind], keep, &tot);
+        const auto tg0 = std::chrono::steady_clock::now();
+        if (tot > 0) {
+            const size_t nb = (size_t)tot;
+            if ((rc = grow(S->gat_rg, sizeof(GatherRange) * rg.size(), err, errlen)) ||
+                (rc = grow(S->cn_v, 8 * nb, err, errlen)))
+                return rc;
+            if (S->h_cn_cap < nb) {
+                if (S->h_cn) (void)hipHostFree(S->h_cn);
+                S->h_cn = nullptr;
+                S->h_cn_cap = 0;
+                const size_t want = nb + nb / 4 + 4096;
+                CK(hipHostMalloc((void **)&S->h_cn, 8 * want, 0));
+                S->h_cn_cap = want;
+            }
+            CK(hipMemcpyAsync(S->gat_rg.p, rg.data(), sizeof(GatherRange) * rg.size(), hipMemcpyHostToDevice, st));
+            const int g_ = (int)std::min<int64_t>((tot + 255) / 256, 16384);
+            hipLaunchKernelGGL(k_cnv_cn_ratio, dim3(g_), dim3(256), 0, st, (const GatherRange *)S->gat_rg.p,
+                               (int)rg.size(), gcw, d_mq, d_rd, d_low, flag, dT, (int32_t)P.rd_min_mapq, tot,
+                               (double *)S->cn_v.p);
+            CK(hipGetLastError());
+            CK(hipMemcpyAsync(S->h_cn, S->cn_v.p, 8 * nb, hipMemcpyDeviceToHost, st));
+            CK(hipStreamSynchronize(st));
+        }
+        const auto tg1 = std::chrono::steady_clock::now();
+        dump.vec(kind == 0 ? "calls0" : "calls1", found[kind]);
+        dump.put(kind == 0 ? "ratios0" : "ratios1", S->h_cn, 8 * (size_t)tot);
+        std::vector<double> cn, cs;
+        const unsigned nt = copy_numbers(S->h_cn, rg, (int)P.ploidy, cn, cs);
+        if (tmg) {
+            const auto tg2 = std::chrono::steady_clock::now();
+            int64_t mx = 0;
+            for (size_t j = 0; j < keep.size(); j++) mx = std::max<int64_t>(mx, rg[j].count);
+            fprintf(stderr, "cnv rows %s: %zu calls, %lld bases (largest %lld), %u threads; gather %.1f ms, copy number %.1f ms\n",
+                    kind == 0 ? "DEL" : "DUP", keep.size(), (long long)tot, (long long)mx, nt,
+                    std::chrono::duration<double, std::milli>(tg1 - tg0).count(),
+                    std::chrono::duration<double, std::milli>(tg2 - tg1).count());
+        }
+        n_rows += format_rows(rows, P, kind, chr_name, found[kind], keep, cn, cs);
+    }
+    dump.put("rows", rows.data() + rows0, rows.size() - rows0);
+    mark("rows");
+    return GROM_OK;
+}
+
+}  // namespace
+
+int cnv_chrom(CnvScratch *S, hipStream_t st, const grom_params &P, uint32_t seed, const char *chr_name,
+              const char *d_ref, int64_t len, int32_t *d_mq, const int32_t *d_rd, const int32_t *d_low,
+              std::string &rows, CnvTiming *timing, char *err, size_t errlen, std::string *side) {
+    const auto t_host0 = std::chrono::steady_clock::now();
+    int rc;
+    if (P.insert_mean < 1) {
+        snprintf(err, errlen, "insert mean %lld below 1", (long long)P.insert_mean);
+        return GROM_E_ARG;
+    }
+    // (window lengths index int32 positions in the walk; -X past a chromosome
+    // only makes every window search stop at the end)
+    if (P.max_rd_window_len < P.min_rd_window_len || P.min_rd_window_len < 1 || P.windows_sampling_factor < 1 ||
+        P.max_rd_window_len > ((int64_t)1 << 30)) {
+        snprintf(err, errlen, "unsupported CNV window parameters (-W %lld -X %lld -A %lld)",
+                 (long long)P.min_rd_window_len, (long long)P.max_rd_window_len, (long long)P.windows_sampling_factor);
+        return GROM_E_ARG;
+    }
+    if ((rc = cnv_init(S, err, errlen))) return rc;
+    Chrom C(S, st, P, chr_name, d_ref, len, d_mq, d_rd, d_low, err, errlen);
+    C.dump.put("params", &P, sizeof(P));
+    C.dump.put("len", &len, 8);
+    C.dump.put("chr", chr_name, strlen(chr_name));
+    if ((rc = C.begin()) || (rc = C.gc_windows()) || (rc = C.depth_statistics()) || (rc = C.sampling(seed)) ||
+        (rc = C.flags_and_z()) || (rc = C.side_file(side)) || (rc = C.windows()) || (rc = C.repeat_override()) ||
+        (rc = C.walk_inputs()) || (rc = C.searches()) || (rc = C.rows_of(rows)))
+        return rc;
+    if (C.tmg) fprintf(stderr, "cnv phases ms:%s\n", C.tlog.c_str());
+    if (timing) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, S->e0, S->e1);
+        timing->ms_device = ms;
+        timing->del_calls = (int64_t)C.found[0].size();
+        timing->dup_calls = (int64_t)C.found[1].size();
+        timing->rows = C.n_rows;
+        timing->ms_host =
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
+    }
+    return GROM_OK;
+}
+

@@ -535,14 +535,14 @@ static int scan_device(Ctx &C, const grom_chrom *ch, const grom_reads *R, grom_o
     hipLaunchKernelGGL(k_scan_tile<NSL>, dim3(grid), dim3(GROM_TILE), 0, st, a, ch->ref, ra, (const ReadMeta *)C.meta.p, \
                        (const int32_t *)C.tlo.p, (const int32_t *)C.thi.p, po, C.d_mq, C.d_hez, n_tiles, d_heavy, pack_max)
         // (GROM_MEM_SLOTS=1, a test hook: the global-slot kernel for any -n)
-        static const bool force_mem_slots = getenv("GROM_MEM_SLOTS") && atoi(getenv("GROM_MEM_SLOTS")) == 1;
+        const bool force_mem_slots = getenv("GROM_MEM_SLOTS") && atoi(getenv("GROM_MEM_SLOTS")) == 1;
         // the register builds first; then the global-slot kernel: every tile
         // when -n exceeds the register builds, else only the tiles with too
         // many reads for the register builds' 16-bit counters (it returns at
         // once when k_scan_tile flagged none)
         uint32_t *d_heavy = (uint32_t *)(misc + 24);
         // (GROM_HEAVY_TILES=1, a test hook: every tile takes the heavy-tile route)
-        static const bool all_heavy = getenv("GROM_HEAVY_TILES") && atoi(getenv("GROM_HEAVY_TILES")) == 1;
+        const bool all_heavy = getenv("GROM_HEAVY_TILES") && atoi(getenv("GROM_HEAVY_TILES")) == 1;
         const int32_t pack_max = all_heavy ? -1 : PACK_MAX_READS;
         const bool mem_all = P.min_snv > GROM_MAX_NAME_SLOTS || force_mem_slots;
         if (mem_all) {
@@ -735,7 +735,7 @@ static int scan_device(Ctx &C, const grom_chrom *ch, const grom_reads *R, grom_o
                 // the CNV path runs on the GPU
                 svt = std::thread([&P, ch, href, &cs, hits, nh, &sv_text, &ctx_text] {
                     SvRowsInput ri{&P, ch->name, href, ch->len, &CafSum::call, &cs};
-                    static const char *rec_prefix = getenv("GROM_SV_HITS_DUMP");  // test hook (sv.h)
+                    const char *rec_prefix = getenv("GROM_SV_HITS_DUMP");  // test hook (sv.h)
                     if (!rec_prefix) {
                         sv_rows(ri, hits, nh, sv_text, ctx_text);
                         return;

@@ -1512,3 +1512,10 @@ void grom_oracle_grom_rand(unsigned int seed, long mx, int n, long *out) {
     glibc_srand(&g_rng, seed);
     for (int i = 0; i < n; i++) out[i] = grom_rand(mx);
 }
+/* the reference's bisects (GROM.c:21630-21860) over l[0..n): 0 bisect_left and
+ * 1 bisect_right on the ints, 2 bisect_right_double on the doubles */
+long grom_oracle_bisect(int which, const int *l, const double *ld, long n, double v) {
+    if (which == 0) return bisect_left(l, (int)v, 0, n);
+    if (which == 1) return bisect_right(l, (int)v, 0, n);
+    return bisect_right_double(ld, v, 0, n);
+}

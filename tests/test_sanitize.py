@@ -20,6 +20,13 @@ uninstrumented and never called) and grom_synth.  The runs cover:
     parameters, reference, the per-base hits, every INV depth query with its
     answer, and the rows the GPU run wrote), replayed on concurrent threads,
     four rounds each, and compared with the recorded rows;
+  - cnvcall.cpp's CNV host arithmetic on inputs recorded from real GPU scans of
+    CNV parity cases whose rows equalled the oracle's (tests/golden/
+    cnvh_*.cnvh.gz, written by tools/record_cnv_host.sh with
+    GROM_CNV_HOST_DUMP: what the host steps read from the device and every
+    result they produced, down to the rows), the records replayed on concurrent
+    threads through the samplers, tables, window plan, z override and the
+    threaded copy-number step, every recorded output compared byte for byte;
   - the device BGZF inflater's host twin (inflate.h) on the synthetic BAM.
 Any sanitizer report fails the test (UBSan is built with
 -fno-sanitize-recover, ASan/TSan exit non-zero).
@@ -81,6 +88,16 @@ def test_host_code_under_sanitizer(san, tmp_path):
     assert len(recs) >= 2
     out = _run([driver, "svrows"] + recs, d)
     assert out.count(": rc 0") == len(recs), out
+    # cnvcall.cpp on recorded GPU-scan inputs, every record on its own thread
+    recs = []
+    for gz in sorted(glob.glob(os.path.join(REPO, "tests", "golden", "cnvh_*.cnvh.gz"))):
+        path = os.path.join(d, os.path.basename(gz)[:-3])
+        with gzip.open(gz, "rb") as fi, open(path, "wb") as fo:
+            fo.write(fi.read())
+        recs.append(path)
+    assert len(recs) >= 2
+    out = _run([driver, "cnvhost"] + recs, d)
+    assert out.count(": 0 mismatches") == len(recs), out
     if san == "asan":  # single-threaded helpers: once is enough
         assert "0 mismatches" in _run([driver, "inflate", "s.bam"], d)
         assert "0 mismatches" in _run([driver, "bai", "s.bam", "3000"], d)

@@ -24,6 +24,12 @@
  *                        recorded GPU-scan inputs (GROM_SV_HITS_DUMP), every
  *                        record on its own thread, four rounds, outputs
  *                        compared with the recorded rows
+ *   cnvhost <rec>...     cnvcall.cpp's CNV host arithmetic (depth statistics,
+ *                        samplers, bin tables, window plan, z override, wsd,
+ *                        the threaded copy numbers, rows) on the inputs
+ *                        recorded from GPU scans (GROM_CNV_HOST_DUMP), every
+ *                        record on its own thread, every recorded output
+ *                        compared byte for byte
  */
 #include <pthread.h>
 #include <stdint.h>
@@ -153,6 +159,38 @@ static void *replay_main(void *arg) {
     return NULL;
 }
 
+int64_t grom_cnv_host_replay(const char *path); /* cnvcall.cpp test hook (cnvcall.h) */
+
+typedef struct {
+    const char *path;
+    int64_t bad;
+} cnvhost_job;
+
+static void *cnvhost_main(void *arg) {
+    cnvhost_job *j = (cnvhost_job *)arg;
+    for (int r = 0; r < 2 && j->bad == 0; r++) j->bad = grom_cnv_host_replay(j->path);
+    return NULL;
+}
+
+static int cmd_cnvhost(int n, char **paths) {
+    cnvhost_job *jobs = calloc((size_t)n, sizeof(cnvhost_job));
+    pthread_t *t = calloc((size_t)n, sizeof(pthread_t));
+    for (int i = 0; i < n; i++) {
+        jobs[i].path = paths[i];
+        pthread_create(&t[i], NULL, cnvhost_main, &jobs[i]);
+    }
+    int bad = 0;
+    for (int i = 0; i < n; i++) {
+        pthread_join(t[i], NULL);
+        if (jobs[i].bad < 0) printf("cnvhost %s: unreadable record (%lld)\n", paths[i], (long long)jobs[i].bad);
+        else printf("cnvhost %s: %lld mismatches\n", paths[i], (long long)jobs[i].bad);
+        bad += jobs[i].bad != 0;
+    }
+    free(jobs);
+    free(t);
+    return bad != 0;
+}
+
 static int cmd_svrows(int n, char **paths) {
     replay_job *jobs = calloc((size_t)n, sizeof(replay_job));
     pthread_t *t = calloc((size_t)n, sizeof(pthread_t));
@@ -173,7 +211,7 @@ static int cmd_svrows(int n, char **paths) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: san_driver cli|bai|fmt|synth|ctx|svrows|inflate|fasta ...\n");
+        fprintf(stderr, "usage: san_driver cli|bai|fmt|synth|ctx|svrows|cnvhost|inflate|fasta ...\n");
         return 2;
     }
     if (!strcmp(argv[1], "cli")) return grom_cli_main(argc - 1, argv + 1);
@@ -182,6 +220,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "synth") && argc >= 3) return cmd_synth(atoll(argv[2]));
     if (!strcmp(argv[1], "ctx")) return cmd_ctx();
     if (!strcmp(argv[1], "svrows") && argc >= 3) return cmd_svrows(argc - 2, argv + 2);
+    if (!strcmp(argv[1], "cnvhost") && argc >= 3) return cmd_cnvhost(argc - 2, argv + 2);
     if (!strcmp(argv[1], "inflate") && argc >= 3) return cmd_inflate(argv[2]);
     if (!strcmp(argv[1], "fasta") && argc >= 3) return cmd_fasta(argv[2]);
     fprintf(stderr, "bad arguments\n");
