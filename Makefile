@@ -10,8 +10,8 @@ LIBDIR  = grom_amd/lib
 BINDIR  = grom_amd/bin
 
 HOST_SRC = grom_amd/csrc/bamio.c grom_amd/csrc/stream.c grom_amd/csrc/tables.c grom_amd/csrc/synth.c grom_amd/csrc/hostapi.c grom_amd/csrc/grom_main.c grom_amd/csrc/pdecode.c
-HOST_OBJ = $(patsubst grom_amd/csrc/%.c,build/%.o,$(HOST_SRC)) build/snvfmt.o build/svcall.o build/cnvcall.o build/inflate_host.o build/devmem.o
-DEV_OBJ = build/scan.o build/cnv.o build/sv.o build/ddecode.o build/baidev.o build/fastadev.o
+HOST_OBJ = $(patsubst grom_amd/csrc/%.c,build/%.o,$(HOST_SRC)) build/snvfmt.o build/svcall.o build/cnvcall.o build/inflate_host.o build/gzip_host.o build/devmem.o
+DEV_OBJ = build/scan.o build/cnv.o build/sv.o build/ddecode.o build/baidev.o build/fastadev.o build/gzipdev.o
 HDRS = include/grom_amd.h grom_amd/csrc/devmem.h grom_amd/csrc/devbuf.h grom_amd/csrc/scan_common.h grom_amd/csrc/bamio.h grom_amd/csrc/stream.h grom_amd/csrc/synth.h grom_amd/csrc/pdecode.h grom_amd/csrc/ddecode.h grom_amd/csrc/cnvcall.h grom_amd/csrc/cnv_bisect.h
 KHDRS = grom_amd/csrc/k_scan_tile.h grom_amd/csrc/device_common.h grom_amd/csrc/snvfmt.h
 
@@ -23,6 +23,12 @@ build/%.o: grom_amd/csrc/%.c $(HDRS)
 
 # the device BGZF inflater's host twin (same decoder, one lane; tests)
 build/inflate_host.o: grom_amd/csrc/inflate_host.cpp grom_amd/csrc/inflate.h $(HDRS)
+	@mkdir -p build
+	$(CXX) -O2 -g -Wall -fPIC -std=c++17 -c $< -o $@
+
+# the parallel gzip read's host twin (gzipinf.h's per-lane code with one lane; tests)
+GZ_HDRS = grom_amd/csrc/gzipplan.h grom_amd/csrc/gzipinf.h grom_amd/csrc/inflate.h
+build/gzip_host.o: grom_amd/csrc/gzip_host.cpp $(GZ_HDRS) $(HDRS)
 	@mkdir -p build
 	$(CXX) -O2 -g -Wall -fPIC -std=c++17 -c $< -o $@
 
@@ -45,7 +51,12 @@ build/baidev.o: grom_amd/csrc/baidev.hip grom_amd/csrc/ddecode.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the reference FASTA read on the device, bgzip-compressed or plain (the decoder's inflater)
-build/fastadev.o: grom_amd/csrc/fastadev.hip grom_amd/csrc/ddecode.h $(HDRS)
+build/fastadev.o: grom_amd/csrc/fastadev.hip grom_amd/csrc/ddecode.h grom_amd/csrc/gzipdev.h $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# one plain gzip stream inflated on the device in parallel (gzipinf.h over inflate.h's decoder)
+build/gzipdev.o: grom_amd/csrc/gzipdev.hip grom_amd/csrc/gzipdev.h $(GZ_HDRS) $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -98,12 +109,12 @@ oracle:
 # kernel tuning variants, loaded with GROM_AMD_LIB=...:
 #   make variant V=w4 VFLAGS=-DGROM_WAVES_PER_EU=4  ->  grom_amd/lib/variants/libgrom_amd_w4.so
 #   make variant V=q0 VFLAGS=-DGI_QUAD=0            (the inflater's bit reader)
-variant: $(HOST_OBJ) build/sv.o build/baidev.o build/fastadev.o
+variant: $(HOST_OBJ) build/sv.o build/baidev.o build/fastadev.o build/gzipdev.o
 	@mkdir -p build/variants $(LIBDIR)/variants
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c grom_amd/csrc/scan.hip -o build/variants/scan_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -ffp-contract=off -c grom_amd/csrc/cnv.hip -o build/variants/cnv_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c grom_amd/csrc/ddecode.hip -o build/variants/ddecode_$(V).o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(LIBDIR)/variants/libgrom_amd_$(V).so build/variants/scan_$(V).o build/variants/cnv_$(V).o build/sv.o build/variants/ddecode_$(V).o build/baidev.o build/fastadev.o $(HOST_OBJ) -lz -lm
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(LIBDIR)/variants/libgrom_amd_$(V).so build/variants/scan_$(V).o build/variants/cnv_$(V).o build/sv.o build/variants/ddecode_$(V).o build/baidev.o build/fastadev.o build/gzipdev.o $(HOST_OBJ) -lz -lm
 
 clean:
 	rm -rf build $(LIBDIR) $(BINDIR)
@@ -121,13 +132,17 @@ SANFLAGS = -fsanitize=thread
 else
 SANFLAGS = -fsanitize=address,undefined -fno-sanitize-recover=undefined
 endif
-SAN_OBJ = $(patsubst grom_amd/csrc/%.c,$(SANDIR)/%.o,$(HOST_SRC)) $(SANDIR)/snvfmt.o $(SANDIR)/inflate_host.o
+SAN_OBJ = $(patsubst grom_amd/csrc/%.c,$(SANDIR)/%.o,$(HOST_SRC)) $(SANDIR)/snvfmt.o $(SANDIR)/inflate_host.o $(SANDIR)/gzip_host.o
 
 $(SANDIR)/%.o: grom_amd/csrc/%.c $(HDRS)
 	@mkdir -p $(SANDIR)
 	$(CC) -O1 -g -fno-omit-frame-pointer -Wall -Wno-alloc-size-larger-than -fPIC $(SANFLAGS) -c $< -o $@
 
 $(SANDIR)/inflate_host.o: grom_amd/csrc/inflate_host.cpp grom_amd/csrc/inflate.h $(HDRS)
+	@mkdir -p $(SANDIR)
+	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -fPIC -std=c++17 $(SANFLAGS) -c $< -o $@
+
+$(SANDIR)/gzip_host.o: grom_amd/csrc/gzip_host.cpp $(GZ_HDRS) $(HDRS)
 	@mkdir -p $(SANDIR)
 	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -fPIC -std=c++17 $(SANFLAGS) -c $< -o $@
 
@@ -165,6 +180,12 @@ $(SANDIR)/devbuf_check: tools/devbuf_check.cpp grom_amd/csrc/devbuf.h grom_amd/c
 	@mkdir -p $(SANDIR)
 	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -std=c++17 $(SANFLAGS) $< -o $@
 
-sanitize: $(SANDIR)/san_driver $(SANDIR)/grom_synth $(SANDIR)/devbuf_check
+# the gzip read's host twin on good and damaged streams: no HIP, no device
+# (tests/test_gzip_host.py)
+$(SANDIR)/gzip_check: tools/gzip_check.cpp $(SANDIR)/gzip_host.o
+	@mkdir -p $(SANDIR)
+	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -std=c++17 $(SANFLAGS) $^ -lz -o $@
+
+sanitize: $(SANDIR)/san_driver $(SANDIR)/grom_synth $(SANDIR)/devbuf_check $(SANDIR)/gzip_check
 
 .PHONY: sanitize

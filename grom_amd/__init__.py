@@ -166,6 +166,13 @@ _SIGS = {
     "grom_fasta_dev_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "grom_fasta_dev_close": (None, [C.c_void_p]),
     "grom_fasta_dev_is_bgzf": (C.c_int, [C.c_void_p]),
+    "grom_fasta_dev_kind": (C.c_int, [C.c_void_p]),
+    "grom_fasta_allow_gzip": (C.c_int, [C.c_int]),
+    "grom_fasta_dev_gzip_stats": (None, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    # the host twin of the device's parallel gzip read (gzip_host.cpp)
+    "grom_gzip_inflate_host": (C.c_int, [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "grom_gzip_free": (None, [C.c_void_p]),
     "grom_fasta_dev_index": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "grom_fasta_dev_entry": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -227,9 +234,39 @@ FASTA_TIMES = ("read_upload_ms", "inflate_ms", "index_kernels_ms", "load_kernels
                "index_wall_ms", "loads_wall_ms")
 
 
+FASTA_KINDS = ("plain", "bgzf", "gzip")
+GZIP_STATS = ("units", "units_guessed", "units_again", "marker_bytes", "members", "max_unit_bytes", "scratch_bytes",
+              "groups")
+GZIP_TIMES = ("guess_ms", "count_ms", "symbols_ms", "handover_ms", "resolve_ms", "crc_ms")
+
+
 class FastaHostOnly(RuntimeError):
-    """The device loader's "host only" answer (a NUL byte in the text, or more
-    headers than the host table keeps): the host code has to read the file."""
+    """The device loader's "host only" answer (a NUL byte in the text, more
+    headers than the host table keeps, or a gzip stream with a stretch too
+    long for one lane): the host code has to read the file."""
+
+
+def allow_gzip_fasta(on: "bool | None") -> "bool | None":
+    """Whether a gzip FASTA that is not BGZF is read as it is (True), refused
+    (False) or follows GROM_FASTA_GZIP at each open (None, the default).
+    Returns the previous setting."""
+    prev = lib().grom_fasta_allow_gzip(-1 if on is None else int(bool(on)))
+    return None if prev < 0 else bool(prev)
+
+
+def gzip_inflate_host(data: bytes, chunk_bytes: int = 0, unit_max_bytes: int = 0, guess_mode: int = 1):
+    """The host twin of the device's parallel gzip read: (text, stats).  Raises
+    FastaHostOnly for a unit over the cap, RuntimeError for a malformed stream."""
+    out, n, st = C.c_void_p(), C.c_int64(), (C.c_int64 * 8)()
+    rc = lib().grom_gzip_inflate_host(data, len(data), chunk_bytes, unit_max_bytes, guess_mode, C.byref(out), C.byref(n), st)
+    stats = dict(zip(GZIP_STATS, (int(v) for v in st)))
+    if rc == FASTA_HOST_ONLY:
+        raise FastaHostOnly("the gzip read reports: host only")
+    check(rc, "grom_gzip_inflate_host")
+    try:
+        return C.string_at(out, n.value), stats
+    finally:
+        lib().grom_gzip_free(out)
 
 
 def _fasta_host_index(path):
@@ -248,11 +285,15 @@ def _fasta_host_index(path):
 
 
 class FastaDevice:
-    """A FASTA (plain or BGZF) brought to GPU `device` (grom_fasta_dev_*)."""
+    """A FASTA (plain, BGZF or -- when allowed -- plain gzip) brought to GPU
+    `device` (grom_fasta_dev_*)."""
 
     def __init__(self, path, device: int = 0):
         self.h = C.c_void_p()
-        check(lib().grom_fasta_dev_open(os.fsencode(path), device, C.byref(self.h)), "grom_fasta_dev_open")
+        rc = lib().grom_fasta_dev_open(os.fsencode(path), device, C.byref(self.h))
+        if rc == FASTA_HOST_ONLY:
+            raise FastaHostOnly("the device open reports: host only")
+        check(rc, "grom_fasta_dev_open")
 
     def close(self):
         if self.h:
@@ -268,6 +309,17 @@ class FastaDevice:
     @property
     def bgzf(self) -> bool:
         return bool(lib().grom_fasta_dev_is_bgzf(self.h))
+
+    @property
+    def kind(self) -> str:
+        """ "plain", "bgzf" or "gzip" """
+        return FASTA_KINDS[lib().grom_fasta_dev_kind(self.h)]
+
+    def gzip_stats(self) -> dict:
+        """A gzip open's figures (grom_fasta_dev_gzip_stats)."""
+        st, ms = (C.c_int64 * 8)(), (C.c_double * 6)()
+        lib().grom_fasta_dev_gzip_stats(self.h, st, ms)
+        return {**dict(zip(GZIP_STATS, (int(v) for v in st))), **dict(zip(GZIP_TIMES, (float(v) for v in ms)))}
 
     def entries(self, n):
         out = []

@@ -4,7 +4,8 @@
 // in whole blocks through two pinned buffers into HBM (DdBgzfFile, ddecode.h,
 // which also builds each read's block table) and its blocks inflated by the
 // decoder's inflater (dd_inflate_launch, one block per lane) into one resident
-// text; a plain file is copied as it is.  The index (grom_fasta_open,
+// text; a plain file is copied as it is; a plain gzip file (one DEFLATE stream
+// per member; GROM_FASTA_GZIP=1) is copied as it is and inflated by gzipdev.hip.  The index (grom_fasta_open,
 // stream.c) and the loader (grom_fasta_load) are then kernels over that text,
 // and give the host code's results bit for bit.  The scratch of those kernels
 // is DevBufs (devbuf.h) accounted as decode memory, freed with the handle; the
@@ -43,6 +44,7 @@
 #include "../../include/grom_amd.h"
 #include "ddecode.h"
 #include "devbuf.h"
+#include "gzipdev.h"
 #include "stream.h"
 
 namespace {
@@ -317,6 +319,9 @@ struct FaScratch {
 
 struct grom_fasta_dev : FaScratch {
     int device = 0, bgzf = 0;
+    int kind = 0;  // grom_fasta_file_kind: 0 plain text, 1 BGZF, 2 gzip that is not BGZF
+    int64_t gz_stats[8] = {};
+    double gz_ms[GZ_DEV_STAGES] = {};
     int64_t piece = (int64_t)256 << 20;
     int64_t size = 0;  // the text's bytes
     uint8_t *text = nullptr;
@@ -384,11 +389,21 @@ int ingest(grom_fasta_dev *d, const char *path) {
     const int64_t ring = std::min<int64_t>(std::max<int64_t>(d->piece, 131072), (int64_t)64 << 20);
     FAK((hipError_t)R.rings(ring, d->bgzf ? (size_t)(ring / 64 + 64) : 0));  // (a plain file has no block table)
     for (int k = 0; k < 2; k++) FAK(hipEventCreateWithFlags(&E.rev[k], hipEventDisableTiming));
+    Buf comp;
     if (!d->bgzf) {
-        d->size = fsize;
-        d->text_cap = (size_t)fsize + FA_TEXT_PAD;
-        if (grom_dev_malloc((void **)&d->text, d->text_cap, GROM_DEVCAT_DECODE) != 0)
-            return d->fail(GROM_E_NOMEM, "device FASTA: hipMalloc(%lld) failed", (long long)d->text_cap);
+        // the file as it is: the text itself, or (gzip) the stream to inflate
+        uint8_t *dst = nullptr;
+        if (d->kind == 2) {
+            FAG(comp, (size_t)fsize + 64);
+            dst = P<uint8_t>(comp);
+            FAK(hipMemsetAsync(dst + fsize, 0, 64, d->st));
+        } else {
+            d->size = fsize;
+            d->text_cap = (size_t)fsize + FA_TEXT_PAD;
+            if (grom_dev_malloc((void **)&d->text, d->text_cap, GROM_DEVCAT_DECODE) != 0)
+                return d->fail(GROM_E_NOMEM, "device FASTA: hipMalloc(%lld) failed", (long long)d->text_cap);
+            dst = d->text;
+        }
         int64_t off = 0;
         for (int64_t k = 0; off < fsize; k++) {
             const int s = (int)(k & 1);
@@ -396,16 +411,23 @@ int ingest(grom_fasta_dev *d, const char *path) {
             const int64_t want = std::min<int64_t>(ring, fsize - off);
             if ((int64_t)fread(R.ring[s], 1, (size_t)want, fp) != want)
                 return d->fail(GROM_E_ARG, "device FASTA: read error at byte %lld", (long long)off);
-            FAK(hipMemcpyAsync(d->text + off, R.ring[s], (size_t)want, hipMemcpyHostToDevice, d->st));
+            FAK(hipMemcpyAsync(dst + off, R.ring[s], (size_t)want, hipMemcpyHostToDevice, d->st));
             FAK(hipEventRecord(E.rev[s], d->st));
             off += want;
         }
         FAK(hipStreamSynchronize(d->st));
         d->ms[0] += now_ms() - t0;
-        return 0;
+        if (d->kind != 2) return 0;
+        // one DEFLATE stream per member, read in parallel (gzipdev.hip); its
+        // scratch is freed when gz_dev_read returns, the compressed copy with `comp`
+        const int rc = gz_dev_read(d->st, dst, fsize, FA_TEXT_PAD, &d->text, &d->text_cap, &d->size, d->gz_stats, d->gz_ms,
+                                   d->err, sizeof(d->err));
+        d->gz_stats[6] += (int64_t)comp.cap;
+        for (int k = 0; k < GZ_DEV_STAGES; k++) d->ms[1] += d->gz_ms[k];
+        return rc;
     }
     // BGZF: the compressed file to HBM in whole blocks, the block table beside it
-    Buf comp, dblk, status, tok, misc;
+    Buf dblk, status, tok, misc;
     FAG(comp, (size_t)fsize + 64);
     std::vector<DdBlock> all;
     int64_t total = 0;
@@ -605,9 +627,9 @@ extern "C" int grom_fasta_dev_open(const char *path, int device, grom_fasta_dev 
         grom_set_last_error(m);
         return GROM_E_ARG;
     }
-    if (kind == 2) {
-        snprintf(m, sizeof(m), "%s is gzip-compressed but not BGZF: recompress it with bgzip (a single DEFLATE stream "
-                 "cannot be read in parallel)", path);
+    if (kind == 2 && !grom_fasta_gzip_allowed()) {
+        snprintf(m, sizeof(m), "%s is gzip-compressed but not BGZF: recompress it with bgzip, or set GROM_FASTA_GZIP=1 to "
+                 "read it as it is", path);
         grom_set_last_error(m);
         return GROM_E_ARG;
     }
@@ -620,6 +642,7 @@ extern "C" int grom_fasta_dev_open(const char *path, int device, grom_fasta_dev 
     grom_fasta_dev *d = new grom_fasta_dev();
     d->device = device;
     d->bgzf = kind == 1;
+    d->kind = kind;
     const char *e = getenv("GROM_FASTA_PIECE_KB");
     if (e && atof(e) > 0) d->piece = (int64_t)(atof(e) * 1024.0);
     d->piece = std::min<int64_t>(std::max<int64_t>(d->piece, 4096), (int64_t)1 << 30);
@@ -631,8 +654,11 @@ extern "C" int grom_fasta_dev_open(const char *path, int device, grom_fasta_dev 
     }();
     d->ms[5] = now_ms() - t0;
     if (rc != 0) {
-        snprintf(m, sizeof(m), "%s (%s)", d->err[0] ? d->err : "device FASTA: open failed", path);
-        grom_set_last_error(m);
+        // (host only: a gzip unit over the cap -- the caller reads the file on the host)
+        if (rc != GROM_FASTA_HOST_ONLY) {
+            snprintf(m, sizeof(m), "%s (%s)", d->err[0] ? d->err : "device FASTA: open failed", path);
+            grom_set_last_error(m);
+        }
         grom_fasta_dev_close(d);
         return rc;
     }
@@ -655,6 +681,13 @@ extern "C" void grom_fasta_dev_close(grom_fasta_dev *d) {
 }
 
 extern "C" int grom_fasta_dev_is_bgzf(const grom_fasta_dev *d) { return d ? d->bgzf : 0; }
+
+extern "C" int grom_fasta_dev_kind(const grom_fasta_dev *d) { return d ? d->kind : -1; }
+
+extern "C" void grom_fasta_dev_gzip_stats(const grom_fasta_dev *d, int64_t stats[8], double ms[6]) {
+    for (int k = 0; k < 8; k++) stats[k] = d ? d->gz_stats[k] : 0;
+    for (int k = 0; k < GZ_DEV_STAGES; k++) ms[k] = d ? d->gz_ms[k] : 0.0;
+}
 
 extern "C" int grom_fasta_dev_index(grom_fasta_dev *d, int *n_out, int64_t *mappable) {
     if (!d) { grom_set_last_error("grom_fasta_dev_index: null handle"); return GROM_E_ARG; }

@@ -854,15 +854,17 @@ static void hip_ready(cli_state *S) {
 /* The -r file opened.  Plain text: the host table and loader, as ever
  * (GROM_FASTA_DEVICE=1: the device loader).  BGZF: the device loader
  * (GROM_FASTA_DEVICE=0, the serial reader and plan-only runs: inflated on the
- * host).  <fasta>.info is read and written either way; for a BGZF file its
- * file_pos are offsets in the inflated text.  The device open waits for the
+ * host).  A gzip file that is not BGZF, with GROM_FASTA_GZIP=1: BGZF's routes
+ * (else refused).  <fasta>.info is read and written either way; for a
+ * compressed file its file_pos are offsets in the inflated text.  The device open waits for the
  * HIP start-up thread. */
 static int cli_fasta_open(cli_state *S, int force_serial) {
     const int kind = grom_fasta_file_kind(S->fasta_name);
     const char *fd = getenv("GROM_FASTA_DEVICE"), *ser = getenv("GROM_SERIAL_DECODE");
     const int serial = force_serial || (ser && atoi(ser) > 0);
-    const int want = (kind == 1 && !(fd && atoi(fd) == 0)) || (kind == 0 && fd && atoi(fd) == 1);
-    if (kind == 2 || !want || serial || g_plan_only) {
+    const int gz = kind == 2 && grom_fasta_gzip_allowed(); /* a gzip file read as it is: BGZF's routes */
+    const int want = ((kind == 1 || gz) && !(fd && atoi(fd) == 0)) || (kind == 0 && fd && atoi(fd) == 1);
+    if ((kind == 2 && !gz) || !want || serial || g_plan_only) {
         if (grom_fasta_open_cached(&S->fa, S->fasta_name) != 0) {
             printf("\nCould not open %s\n", S->fasta_name);
             if (kind == 2) printf("%s\n", grom_last_error());
@@ -876,7 +878,17 @@ static int cli_fasta_open(cli_state *S, int force_serial) {
     const long kept = S->fa.n > 0 ? 0 : S->fa.mappable;
     hip_ready(S);
     grom_fasta_dev *d = NULL;
-    if (grom_fasta_dev_open(S->fasta_name, S->device, &d) != 0) {
+    const int orc = grom_fasta_dev_open(S->fasta_name, S->device, &d);
+    if (orc == GROM_FASTA_HOST_ONLY) { /* a gzip stream with a stretch too long for one lane */
+        fprintf(stderr, "grom: reading %s on the host\n", S->fasta_name);
+        grom_fasta_close(&S->fa);
+        if (grom_fasta_open_cached(&S->fa, S->fasta_name) != 0) {
+            printf("\nCould not open %s\n%s\n", S->fasta_name, grom_last_error());
+            return -1;
+        }
+        return 0;
+    }
+    if (orc != 0) {
         printf("\nCould not open %s\n%s\n", S->fasta_name, grom_last_error());
         return -1;
     }
@@ -2012,8 +2024,17 @@ static int cli_run(int argc, char **argv, int force_serial) {
         grom_fasta_dev_times(g_fdev, ms);
         fprintf(stderr, "grom: device FASTA loader (%s, device %d): file read + upload %.1f ms, inflate %.1f ms, index pass "
                         "kernels %.1f ms, load kernels %.1f ms, copies to the host %.1f ms; wall: open %.1f ms, index %.1f ms, "
-                        "loads %.1f ms\n", grom_fasta_dev_is_bgzf(g_fdev) ? "BGZF" : "plain text", g_fdev_device, ms[0], ms[1],
-                ms[2], ms[3], ms[4], ms[5], ms[6], ms[7]);
+                        "loads %.1f ms\n", grom_fasta_dev_is_bgzf(g_fdev) ? "BGZF" : grom_fasta_dev_kind(g_fdev) == 2 ? "gzip" : "plain text",
+                g_fdev_device, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6], ms[7]);
+        if (grom_fasta_dev_kind(g_fdev) == 2) {
+            int64_t gs[8];
+            double gm[6];
+            grom_fasta_dev_gzip_stats(g_fdev, gs, gm);
+            fprintf(stderr, "grom: gzip on the device: %lld units (%lld from guesses, %lld decoded again) in %lld members, "
+                            "%lld marker bytes, scratch %.1f MB; guess %.1f ms, count %.1f ms, symbols %.1f ms, hand-over "
+                            "%.1f ms, resolve %.1f ms, CRC %.1f ms\n", (long long)gs[0], (long long)gs[1], (long long)gs[2],
+                    (long long)gs[4], (long long)gs[3], gs[6] / 1048576.0, gm[0], gm[1], gm[2], gm[3], gm[4], gm[5]);
+        }
     }
     tables_join(S);
     for (int d = 0; d < S->n_init; d++) grom_dev_fini(d);

@@ -7,6 +7,7 @@
 #include <math.h>
 #include <pthread.h>
 #include <unistd.h>
+#include <zlib.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -79,14 +80,55 @@ static int fasta_inflate_host(const char *path, char **mem, long *len) {
     return 0;
 }
 
+/* a plain gzip file (every member) inflated whole through zlib */
+static int fasta_gunzip_host(const char *path, char **mem, long *len) {
+    gzFile g = gzopen(path, "rb");
+    if (!g) return -1;
+    gzbuffer(g, 1 << 20);
+    size_t cap = (size_t)1 << 20, n = 0;
+    char *b = malloc(cap);
+    int rc = b ? 0 : -1;
+    while (rc == 0) {
+        if (cap - n < ((size_t)1 << 19)) {
+            char *nb = realloc(b, cap * 2);
+            if (!nb) { rc = -1; break; }
+            b = nb;
+            cap *= 2;
+        }
+        const int k = gzread(g, b + n, (unsigned)(cap - n > ((size_t)1 << 30) ? (size_t)1 << 30 : cap - n));
+        if (k < 0) rc = -1;
+        if (k <= 0) break;
+        n += (size_t)k;
+    }
+    if (gzclose(g) != Z_OK) rc = -1; /* (a CRC or length that does not match, a stream cut short) */
+    if (rc != 0) { free(b); return -1; }
+    *mem = b;
+    *len = (long)n;
+    return 0;
+}
+
+static int g_allow_gzip = -1;
+
+int grom_fasta_allow_gzip(int mode) {
+    const int prev = g_allow_gzip;
+    if (mode >= -1 && mode <= 1) g_allow_gzip = mode;
+    return prev;
+}
+
+int grom_fasta_gzip_allowed(void) {
+    if (g_allow_gzip >= 0) return g_allow_gzip;
+    const char *e = getenv("GROM_FASTA_GZIP");
+    return e && atoi(e) != 0;
+}
+
 int grom_fasta_attach(grom_fasta *f, const char *path) {
     if (f->fh) return 0;
     const int kind = grom_fasta_file_kind(path);
     if (kind < 0) return -1;
-    if (kind == 2) {
+    if (kind == 2 && !grom_fasta_gzip_allowed()) {
         char m[4400];
-        snprintf(m, sizeof(m), "%s is gzip-compressed but not BGZF: recompress it with bgzip (a single DEFLATE stream "
-                 "cannot be read in parallel)", path);
+        snprintf(m, sizeof(m), "%s is gzip-compressed but not BGZF: recompress it with bgzip, or set GROM_FASTA_GZIP=1 to "
+                 "read it as it is", path);
         grom_set_last_error(m);
         return -1;
     }
@@ -94,9 +136,9 @@ int grom_fasta_attach(grom_fasta *f, const char *path) {
         f->fh = fopen(path, "r");
         return f->fh ? 0 : -1;
     }
-    if (fasta_inflate_host(path, &f->mem, &f->mem_len) != 0) {
+    if ((kind == 1 ? fasta_inflate_host(path, &f->mem, &f->mem_len) : fasta_gunzip_host(path, &f->mem, &f->mem_len)) != 0) {
         char m[4400];
-        snprintf(m, sizeof(m), "%s: a BGZF block does not inflate", path);
+        snprintf(m, sizeof(m), kind == 1 ? "%s: a BGZF block does not inflate" : "%s: the gzip stream does not inflate", path);
         grom_set_last_error(m);
         return -1;
     }

@@ -40,9 +40,12 @@ typedef struct grom_fasta {
     long mem_len;
 } grom_fasta;
 
-/* what a -r file holds: 0 plain text, 1 BGZF, 2 gzip that is not BGZF (refused:
- * one DEFLATE stream cannot be inflated block-parallel), -1 it does not open */
+/* what a -r file holds: 0 plain text, 1 BGZF, 2 gzip that is not BGZF (refused
+ * unless grom_fasta_gzip_allowed), -1 it does not open */
 int grom_fasta_file_kind(const char *path);
+/* a gzip file that is not BGZF is read: grom_fasta_allow_gzip's mode, or with
+ * mode -1 GROM_FASTA_GZIP (read at every call) */
+int grom_fasta_gzip_allowed(void);
 /* the index's name rule on one header chunk (line[0] == '>', L bytes, no NUL):
  * bytes 1.. to the first non-graph byte, lower-cased, at most
  * GROM_MAX_CHR_NAME_LEN - 1 of them; returns name_len */
@@ -53,8 +56,8 @@ void grom_fasta_info_load(grom_fasta *f, const char *path);
 void grom_fasta_info_save(const grom_fasta *f, const char *path);
 /* a table that holds n entries (grom_fasta_info_load's and the device index's) */
 int grom_fasta_reserve(grom_fasta *f, int n);
-/* open the stream of a table-only grom_fasta (a BGZF file is inflated on the
- * host and read through fmemopen); 0, -1 */
+/* open the stream of a table-only grom_fasta (a BGZF file, or an allowed gzip
+ * file through zlib, is inflated on the host and read through fmemopen); 0, -1 */
 int grom_fasta_attach(grom_fasta *f, const char *path);
 
 /* plain text, or BGZF inflated on the host */

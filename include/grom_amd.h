@@ -498,10 +498,39 @@ typedef struct grom_fasta_dev grom_fasta_dev;
 #define GROM_FASTA_HOST_ONLY (-100)
 /* the file's bytes brought to `device` (BGZF blocks inflated there).  0 or a
  * negative GROM_E_* code: GROM_E_NODEV no such device, GROM_E_ARG a file that
- * does not open, a gzip file that is not BGZF (the message says to recompress
- * with bgzip), a block that does not inflate.  GROM_FASTA_PIECE_KB sets the
- * bytes per upload, inflate launch and scan piece (default 262144 = 256 MB). */
+ * does not open, a gzip file that is not BGZF while that is not allowed (the
+ * message says to recompress with bgzip or to set GROM_FASTA_GZIP=1), a block
+ * or stream that does not inflate, a gzip member whose CRC-32 or ISIZE does
+ * not match.  GROM_FASTA_PIECE_KB sets the bytes per upload, inflate launch
+ * and scan piece (default 262144 = 256 MB).
+ * A gzip file that is not BGZF (one DEFLATE stream per member), when allowed,
+ * is inflated on the device in parallel: block starts
+ * guessed per chunk of GROM_GZIP_CHUNK_KB compressed bytes (default 32; may be
+ * fractional) and verified by the chain from the member's first block;
+ * GROM_GZIP_GUESS=0 makes no guesses, =2 wrong ones (tests).  A stretch of
+ * more than GROM_GZIP_UNIT_MAX_KB compressed bytes (default 1024) without a
+ * usable start returns GROM_FASTA_HOST_ONLY: read the file with the host code. */
 int grom_fasta_dev_open(const char *path, int device, grom_fasta_dev **out);
+/* whether a gzip file that is not BGZF is read (device and host code alike):
+ * 1 yes, 0 refused, -1 (the default) as GROM_FASTA_GZIP says at each open.
+ * Returns the previous mode. */
+int grom_fasta_allow_gzip(int mode);
+/* 0 plain text, 1 BGZF, 2 gzip that is not BGZF */
+int grom_fasta_dev_kind(const grom_fasta_dev *d);
+/* a gzip open's figures.  stats = {units, units taken from guesses, units
+ * decoded again from the chain's position, marker bytes (symbols that named
+ * the window before their unit), members, the largest unit's compressed
+ * bytes, peak scratch bytes, hand-over groups}; ms (HIP events) = {guess,
+ * count/verify, symbolic decode, window hand-over, resolve, CRC-32} */
+void grom_fasta_dev_gzip_stats(const grom_fasta_dev *d, int64_t stats[8], double ms[6]);
+/* the host twin of the device's gzip read (tests): the same stages with one
+ * lane.  in[0..n) is the gzip file; chunk_bytes <= 0: one chunk;
+ * unit_max_bytes <= 0: no cap; guess_mode as GROM_GZIP_GUESS.  0 and *out
+ * (release with grom_gzip_free), GROM_FASTA_HOST_ONLY, or GROM_E_ARG for a
+ * malformed stream; stats as above */
+int grom_gzip_inflate_host(const uint8_t *in, int64_t n, int64_t chunk_bytes, int64_t unit_max_bytes, int guess_mode,
+                           uint8_t **out, int64_t *out_len, int64_t stats[8]);
+void grom_gzip_free(uint8_t *p);
 void grom_fasta_dev_close(grom_fasta_dev *d);
 /* 1 when the file is BGZF, 0 plain text */
 int grom_fasta_dev_is_bgzf(const grom_fasta_dev *d);
@@ -525,8 +554,8 @@ void grom_fasta_dev_release(grom_fasta_dev *d, const void *dev_ptr);
 /* ms = {file read + upload wall, inflate (HIP events), index pass kernels,
  * load kernels, load device-to-host copies (wall), open wall, index wall, loads wall} */
 void grom_fasta_dev_times(const grom_fasta_dev *d, double ms[8]);
-/* the host code by path (grom_fasta_open / grom_fasta_load; BGZF inflated on
- * the host): up to cap entries filled, returns the number of entries or
+/* the host code by path (grom_fasta_open / grom_fasta_load; BGZF, or an
+ * allowed gzip file, inflated on the host): up to cap entries filled, returns the number of entries or
  * negative; load returns the loader's length (bytes copied when it fits cap) */
 int grom_fasta_host_index(const char *path, int cap, int64_t *mappable, char *names, int *name_len, int64_t *file_pos,
                           int64_t *len);
