@@ -9,10 +9,10 @@ HIPFLAGS ?= -O3 -g --offload-arch=$(ARCH) -fPIC -std=c++17 -Wall -pthread
 LIBDIR  = grom_amd/lib
 BINDIR  = grom_amd/bin
 
-HOST_SRC = grom_amd/csrc/bamio.c grom_amd/csrc/stream.c grom_amd/csrc/tables.c grom_amd/csrc/synth.c grom_amd/csrc/hostapi.c grom_amd/csrc/grom_main.c grom_amd/csrc/pdecode.c
+HOST_SRC = grom_amd/csrc/cli_settings.c grom_amd/csrc/ctxpost.c grom_amd/csrc/bamio.c grom_amd/csrc/stream.c grom_amd/csrc/tables.c grom_amd/csrc/synth.c grom_amd/csrc/hostapi.c grom_amd/csrc/grom_main.c grom_amd/csrc/pdecode.c
 HOST_OBJ = $(patsubst grom_amd/csrc/%.c,build/%.o,$(HOST_SRC)) build/snvfmt.o build/svcall.o build/cnvcall.o build/inflate_host.o build/gzip_host.o build/devmem.o
 DEV_OBJ = build/scan.o build/cnv.o build/sv.o build/ddecode.o build/baidev.o build/fastadev.o build/gzipdev.o
-HDRS = include/grom_amd.h grom_amd/csrc/devmem.h grom_amd/csrc/devbuf.h grom_amd/csrc/scan_common.h grom_amd/csrc/bamio.h grom_amd/csrc/stream.h grom_amd/csrc/synth.h grom_amd/csrc/pdecode.h grom_amd/csrc/ddecode.h grom_amd/csrc/cnvcall.h grom_amd/csrc/cnv_bisect.h
+HDRS = include/grom_amd.h grom_amd/csrc/devmem.h grom_amd/csrc/devbuf.h grom_amd/csrc/scan_common.h grom_amd/csrc/bamio.h grom_amd/csrc/stream.h grom_amd/csrc/synth.h grom_amd/csrc/pdecode.h grom_amd/csrc/ddecode.h grom_amd/csrc/cnvcall.h grom_amd/csrc/cnv_bisect.h grom_amd/csrc/cli_settings.h grom_amd/csrc/ctxpost.h
 KHDRS = grom_amd/csrc/k_scan_tile.h grom_amd/csrc/device_common.h grom_amd/csrc/snvfmt.h
 
 all: $(LIBDIR)/libgrom_amd.so $(BINDIR)/grom $(BINDIR)/grom_synth $(BINDIR)/gromc_binding oracle
@@ -167,7 +167,7 @@ $(SANDIR)/devmem.o: grom_amd/csrc/devmem.cpp $(HDRS)
 	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -fPIC -std=c++17 -pthread -I/opt/rocm/include \
 	    -D__HIP_PLATFORM_AMD__ $(SANFLAGS) -c $< -o $@
 
-$(SANDIR)/san_driver: tools/san_driver.c $(SAN_OBJ) $(SANDIR)/svcall.o $(SANDIR)/cnvcall.o $(SANDIR)/devmem.o $(DEV_OBJ)
+$(SANDIR)/san_driver: tools/san_driver.c $(HDRS) $(SAN_OBJ) $(SANDIR)/svcall.o $(SANDIR)/cnvcall.o $(SANDIR)/devmem.o $(DEV_OBJ)
 	$(CXX) -O1 -g -fno-omit-frame-pointer $(SANFLAGS) -x c tools/san_driver.c -x none $(SAN_OBJ) $(SANDIR)/svcall.o $(SANDIR)/cnvcall.o $(SANDIR)/devmem.o $(DEV_OBJ) \
 	    -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lz -lm -ldl -lpthread -o $@
 

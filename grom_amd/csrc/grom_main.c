@@ -7,11 +7,10 @@
  * order.  The per-chromosome scan (count_discordant_pairs, GROM.c:1432) runs
  * on the GPU through include/grom_amd.h.
  *
- * Not yet restated (the build reports them rather than guessing): -f
- * (tab-separated output).  Options that steer parts of the reference outside
- * the implemented scan rows are accepted and recorded.
+ * Options that steer parts of the reference outside the implemented scan rows
+ * are accepted and recorded.  The GROM_* environment knobs are read once per
+ * run (cli_settings.c lists them); the translocation post-pass is ctxpost.c.
  */
-#include <ctype.h>
 #include <dirent.h>
 #include <pthread.h>
 #include <stdio.h>
@@ -25,10 +24,11 @@
 
 #include "../../include/grom_amd.h"
 #include "bamio.h"
+#include "cli_settings.h"
+#include "ctxpost.h"
 #include "ddecode.h"
 #include "stream.h"
 #include "pdecode.h"
-#include "ddecode.h"
 
 static const char *VERSION = "GROM, Version 1.0.1\n"; /* g_version_name, GROM.c:690 */
 
@@ -76,9 +76,8 @@ static void print_help(void) {
     printf("\n");
 }
 
-static void header(FILE *f, const char *fasta_name, int ctx) {
-    /* GROM.c:20517-20565 (main VCF) and GROM.c:22612-22651 (.ctx.vcf) */
-    const char *pin = getenv("GROM_FILEDATE");
+static void header(FILE *f, const char *fasta_name, int ctx, const char *pin) {
+    /* GROM.c:20517-20565 (main VCF) and GROM.c:22612-22651 (.ctx.vcf); `pin`: GROM_FILEDATE */
     fprintf(f, "##fileformat=VCFv4.2\n");
     if (pin) {
         fprintf(f, "##fileDate=%s\n", pin);
@@ -95,43 +94,39 @@ static void header(FILE *f, const char *fasta_name, int ctx) {
     fprintf(f, "##INFO=<ID=END,Number=1,Type=Integer,Description=\"End position of the structural variant\">\n");
     if (!ctx) fprintf(f, "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n");
     static const char *fmt_lines[][2] = {
-        {"SPR", "Float\",Description=\"Probability of start breakpoint evidence occurring by chance"},
-        {"EPR", "Float\",Description=\"Probability of end breakpoint evidence occurring by chance"},
-        {"SEV", "Integer\",Description=\"Evidence supporting variant at start breakpoint"},
-        {"EEV", "Integer\",Description=\"Evidence supporting variant at end breakpoint"},
-        {"SRD", "Integer\",Description=\"Physical read depth at start breakpoint"},
-        {"ERD", "Integer\",Description=\"Physical read depth at end breakpoint"},
-        {"SCO", "Integer\",Description=\"Concordant pairs at start breakpoint"},
-        {"ECO", "Integer\",Description=\"Concordant pairs at end breakpoint"},
-        {"SOT", "Integer\",Description=\"Count of distinct SVs with evidence at start breakpoint"},
-        {"EOT", "Integer\",Description=\"Count of distinct SVs with evidence at end breakpoint"},
-        {"SSC", "Integer\",Description=\"Soft-clipped reads at start breakpoint"},
-        {"ESC", "Integer\",Description=\"Soft-clipped at end breakpoint"},
-        {"SFR", "Integer\",Description=\"Position of first read supporting start breakpoint"},
-        {"SLR", "Integer\",Description=\"Position of last read supporting start breakpoint"},
-        {"EFR", "Integer\",Description=\"Position of first read supporting end breakpoint"},
-        {"ELR", "Integer\",Description=\"Position of last read supporting end breakpoint"},
-        {"AF", "Float\",Description=\"Allele frequency (high mapping quality reads)"},
-        {"PR", "Float\",Description=\"Probability of SNV evidence occurring by chance"},
-        {"A", "Integer\",Description=\"A nucleotides (high mapping quality reads)"},
-        {"C", "Integer\",Description=\"C nucleotides (high mapping quality reads)"},
-        {"G", "Integer\",Description=\"G nucleotides (high mapping quality reads)"},
-        {"T", "Integer\",Description=\"T nucleotides (high mapping quality reads)"},
-        {"AL", "Integer\",Description=\"A nucleotides (low mapping quality reads)"},
-        {"CL", "Integer\",Description=\"C nucleotides (low mapping quality reads)"},
-        {"GL", "Integer\",Description=\"G nucleotides (low mapping quality reads)"},
-        {"TL", "Integer\",Description=\"T nucleotides (low mapping quality reads)"},
-        {"BQ", "Float\",Description=\"Average base quality (all reads)"},
-        {"MQ", "Float\",Description=\"Average mapping quality (all reads)"},
-        {"PIR", "Float\",Description=\"Average distance of SNV from DNA fragment end)"},
-        {"FS", "Integer\",Description=\"SNV reads mapped to forward strand)"},
+        {"SPR", "Float,Description=\"Probability of start breakpoint evidence occurring by chance"},
+        {"EPR", "Float,Description=\"Probability of end breakpoint evidence occurring by chance"},
+        {"SEV", "Integer,Description=\"Evidence supporting variant at start breakpoint"},
+        {"EEV", "Integer,Description=\"Evidence supporting variant at end breakpoint"},
+        {"SRD", "Integer,Description=\"Physical read depth at start breakpoint"},
+        {"ERD", "Integer,Description=\"Physical read depth at end breakpoint"},
+        {"SCO", "Integer,Description=\"Concordant pairs at start breakpoint"},
+        {"ECO", "Integer,Description=\"Concordant pairs at end breakpoint"},
+        {"SOT", "Integer,Description=\"Count of distinct SVs with evidence at start breakpoint"},
+        {"EOT", "Integer,Description=\"Count of distinct SVs with evidence at end breakpoint"},
+        {"SSC", "Integer,Description=\"Soft-clipped reads at start breakpoint"},
+        {"ESC", "Integer,Description=\"Soft-clipped at end breakpoint"},
+        {"SFR", "Integer,Description=\"Position of first read supporting start breakpoint"},
+        {"SLR", "Integer,Description=\"Position of last read supporting start breakpoint"},
+        {"EFR", "Integer,Description=\"Position of first read supporting end breakpoint"},
+        {"ELR", "Integer,Description=\"Position of last read supporting end breakpoint"},
+        {"AF", "Float,Description=\"Allele frequency (high mapping quality reads)"},
+        {"PR", "Float,Description=\"Probability of SNV evidence occurring by chance"},
+        {"A", "Integer,Description=\"A nucleotides (high mapping quality reads)"},
+        {"C", "Integer,Description=\"C nucleotides (high mapping quality reads)"},
+        {"G", "Integer,Description=\"G nucleotides (high mapping quality reads)"},
+        {"T", "Integer,Description=\"T nucleotides (high mapping quality reads)"},
+        {"AL", "Integer,Description=\"A nucleotides (low mapping quality reads)"},
+        {"CL", "Integer,Description=\"C nucleotides (low mapping quality reads)"},
+        {"GL", "Integer,Description=\"G nucleotides (low mapping quality reads)"},
+        {"TL", "Integer,Description=\"T nucleotides (low mapping quality reads)"},
+        {"BQ", "Float,Description=\"Average base quality (all reads)"},
+        {"MQ", "Float,Description=\"Average mapping quality (all reads)"},
+        {"PIR", "Float,Description=\"Average distance of SNV from DNA fragment end)"},
+        {"FS", "Integer,Description=\"SNV reads mapped to forward strand)"},
     };
-    for (size_t i = 0; i < sizeof(fmt_lines) / sizeof(fmt_lines[0]); i++) {
-        /* the Type= value is unquoted in GROM's text; rebuild it exactly */
-        const char *rest = fmt_lines[i][1];
-        const char *q = strchr(rest, '"');
-        fprintf(f, "##FORMAT=<ID=%s,Number=1,Type=%.*s%s\">\n", fmt_lines[i][0], (int)(q - rest), rest, q + 1);
-    }
+    for (size_t i = 0; i < sizeof(fmt_lines) / sizeof(fmt_lines[0]); i++)
+        fprintf(f, "##FORMAT=<ID=%s,Number=1,Type=%s\">\n", fmt_lines[i][0], fmt_lines[i][1]);
     if (!ctx) {
         fprintf(f, "##FORMAT=<ID=SD,Number=1,Type=Float,Description=\"CNV standard deviation\"\n");
         fprintf(f, "##FORMAT=<ID=Z,Number=1,Type=Float,Description=\"CNV probability score\"\n");
@@ -191,23 +186,6 @@ typedef struct {
     char *target; /* BAM name the SA/XP chromosome test compares with (GROM.c:1894-1961, 7431) */
 } chrom_plan;
 
-static int g_plan_only = 0; /* GROM_PLAN_ONLY: report the record plan, no GPU */
-
-/* the device FASTA loader (fastadev.hip) of this run: a BGZF -r by default, a
- * plain one with GROM_FASTA_DEVICE=1.  One thread at a time uses the handle */
-static grom_fasta_dev *g_fdev = NULL;
-static int g_fdev_device = -1;
-static pthread_mutex_t g_fdev_mu = PTHREAD_MUTEX_INITIALIZER;
-
-static void plan_release_dref(chrom_plan *c) {
-    if (!c->d_ref) return;
-    pthread_mutex_lock(&g_fdev_mu);
-    if (g_fdev) grom_fasta_dev_release(g_fdev, c->d_ref);
-    c->d_ref = NULL;
-    pthread_mutex_unlock(&g_fdev_mu);
-}
-static const char *g_side_base; /* -o name: the -N side files are named after it */
-
 static double clock_gettime_s(void) {
     struct timespec t;
     clock_gettime(CLOCK_MONOTONIC, &t);
@@ -257,138 +235,70 @@ static void textbuf_add(textbuf *t, const char *s, size_t n) {
     t->p[t->len] = 0;
 }
 
-/* main's translocation post-pass (GROM.c:22400-22770): the raw CTX rows of
- * every chromosome are read back, each breakpoint is paired with a mate row
- * (its chromosome and mate chromosome swapped, positions within
- * insert_max - 2*lseq, orientations consistent), the weaker of two nearby
- * paired rows is dropped with its mate, and the rest are written as BND rows. */
+/* one run's state: everything the two input paths share */
 typedef struct {
-    int type, chr, pos, rd, conc, other, mchr, mpos, rs, re, mateid, keep;
-    double binom, ev, hez;
-} ctx_row_t;
+    grom_params P;
+    cli_settings env; /* the GROM_* knobs, read at the run's start */
+    /* grom_cli_main's flag, which outlives a run's second attempt: set once
+     * the streamed run printed the insert lines, so that the serial rerun
+     * after a late fallback (the index plan contradicted mid-file) does not
+     * print them again and stdout reads as one run */
+    int *insert_printed;
+    const char *bam_name, *fasta_name, *out_name;
+    const char *side_base; /* -o name: the -N side files are named after it */
+    long max_chr_len;
+    double num_sd;
+    int device, force_serial;
+    /* the device plan (plan_devices) */
+    int n_dev;                        /* GPUs, from `device` on */
+    int wdev[CLI_MAX_WORKERS], n_work; /* scan worker -> GPU */
+    int n_init;                       /* library contexts made */
+    bam_hdr hdr;
+    grom_fasta fa;
+    /* the device FASTA loader (fastadev.hip) of this run: a BGZF -r by
+     * default, a plain one with GROM_FASTA_DEVICE=1.  One thread at a time
+     * uses the handle */
+    grom_fasta_dev *fdev;
+    pthread_mutex_t fdev_mu;
+    double *hez, *mq;
+    pthread_t tables_thr;
+    int tables_started;
+    chrom_plan *plan; /* candidates in BAM order (preliminary: before the length test) */
+    int n_cand;
+    char ctx_name[4096];
+    /* GROM_VCF_SEGS (a multi-GPU rank's run): where each chromosome's rows lie
+     * in the VCF, "chromosome<TAB>offset<TAB>bytes" per line, so a merge of
+     * the ranks' files copies byte ranges without reading the rows
+     * (grom_amd.shard.merge_rank_outputs_parallel) */
+    textbuf vcf_segs;
+    double t_cli0, t_cand; /* CLI start, candidates (FASTA lengths) done */
+    double t_load;         /* process start to the CLI's start (program and library loading) */
+    double t_scans, t_pdclose, t_outputs; /* scans done, decoder closed, outputs written */
+    double t_decclose;                     /* the decoder's host side closed */
+    pthread_t hip_thr;     /* HIP runtime start-up, beside the header/FASTA/index work */
+    int hip_started, hip_done;
+    /* -P n (1..256, GROM.c:21923-21927): every chromosome reads its own
+     * target's records (bam_fetch, GROM.c:21051-21064 and the -c children of
+     * GROM.c:549-599) -- pd_set_fetch_mode; GROM_P_SERIAL=1 keeps the serial
+     * stream's input (a one-process run's rows) on n GPUs */
+    int fetch;
+    /* -c chr,sub,start,end (GROM.c:21928-21930): one child of a -P n run --
+     * BAM target `one_chrom` alone, read through bam_fetch, its rows to
+     * OUT.<target>-<sub> and its raw CTX rows to OUT.<target>-<sub>.ctx, no
+     * header, no translocation post-pass (the parent concatenates and pairs,
+     * GROM.c:603-624, 22400), the insert statistics from <bam>.mean
+     * (GROM.c:22253-22257).  Whole chromosomes only (start 0, end at or past
+     * the chromosome's end: the children -P n forks without -R). */
+    int one_chrom, sub_child, sub_start, sub_end;
+    char part_name[4096];
+} cli_state;
 
-static void ctx_postpass(const char *raw, size_t raw_len, const bam_hdr *hdr, int Mx, int glseq, int vcf, FILE *out) {
-    int n_t = hdr->n_ref;
-    char **lc = calloc(n_t > 0 ? n_t : 1, sizeof(char *));
-    for (int a = 0; a < n_t; a++) {
-        size_t L = strlen(hdr->ref_name[a]);
-        lc[a] = malloc(L + 1);
-        for (size_t b = 0; b <= L; b++) lc[a][b] = (char)tolower((unsigned char)hdr->ref_name[a][b]);
-    }
-    int n = 0, cap = 1024;
-    ctx_row_t *rw = calloc(cap, sizeof(ctx_row_t));
-    size_t off = 0;
-    while (raw && off < raw_len) {
-        const char *e = memchr(raw + off, '\n', raw_len - off);
-        size_t ll = e ? (size_t)(e - (raw + off)) : raw_len - off;
-        char *line = malloc(ll + 1);
-        memcpy(line, raw + off, ll);
-        line[ll] = 0;
-        off += ll + (e ? 1 : 0);
-        if (n == cap) { cap *= 2; rw = realloc(rw, cap * sizeof(ctx_row_t)); }
-        ctx_row_t *q = &rw[n++];
-        memset(q, 0, sizeof(*q));
-        char *save = NULL, *t = strtok_r(line, "\t", &save);
-        q->type = t ? (strcmp(t, "CTX_F") == 0 ? 6 : strcmp(t, "CTX_R") == 0 ? 7 : -1) : -1; /* g_sv_types */
-        t = strtok_r(NULL, "\t", &save);
-        q->chr = -1;
-        if (t) {
-            char tl[1024];
-            size_t L = strlen(t);
-            if (L > sizeof(tl) - 1) L = sizeof(tl) - 1;
-            for (size_t b = 0; b < L; b++) tl[b] = (char)tolower((unsigned char)t[b]);
-            tl[L] = 0;
-            for (int a = 0; a < n_t; a++)
-                if (strcmp(lc[a], tl) == 0) { q->chr = a; break; }
-        }
-        int *ifld[] = {&q->pos, NULL, NULL, &q->rd, &q->conc, &q->other, &q->mchr, &q->mpos, &q->rs, &q->re, NULL};
-        double *dfld[] = {NULL, &q->binom, &q->ev, NULL, NULL, NULL, NULL, NULL, NULL, NULL, &q->hez};
-        for (int k = 0; k < 11; k++) {
-            t = strtok_r(NULL, "\t", &save);
-            if (ifld[k]) *ifld[k] = t ? atoi(t) : 0;
-            else *dfld[k] = t ? atof(t) : 0;
-        }
-        free(line);
-    }
-    const int span = Mx - 2 * glseq;
-    for (int b = 0; b < n; b++) { rw[b].keep = 0; rw[b].mateid = -1; }
-    for (int b = 0; b < n; b++)
-        for (int c = 0; c < n; c++) {
-            if (!(rw[b].chr == rw[c].mchr && rw[c].chr == rw[b].mchr)) continue;
-            if (!(abs(rw[b].pos - abs(rw[c].mpos)) < span && abs(rw[c].pos - abs(rw[b].mpos)) < span)) continue;
-            const int bo = (rw[b].type == 6 && rw[c].mpos >= 0) || (rw[b].type == 7 && rw[c].mpos < 0);
-            const int co = (rw[c].type == 6 && rw[b].mpos >= 0) || (rw[c].type == 7 && rw[b].mpos < 0);
-            if (bo && co) {
-                rw[b].keep = 1;
-                rw[b].mateid = c;
-                rw[b].mpos = rw[b].mpos < 0 ? -rw[c].pos : rw[c].pos;
-            }
-        }
-    for (int b = 0; b < n; b++)
-        for (int c = 0; c < n; c++) {
-            if (b == c || rw[b].chr != rw[c].chr || rw[b].mchr != rw[c].mchr) continue;
-            if (!(abs(rw[b].pos - rw[c].pos) < span && abs(abs(rw[b].mpos) - abs(rw[c].mpos)) < span)) continue;
-            if (rw[b].keep == 1 && rw[c].keep == 1 && (rw[b].binom > rw[c].binom || (rw[b].binom == rw[c].binom && b > c))) {
-                rw[b].keep = 0;
-                if (rw[b].mateid >= 0) rw[rw[b].mateid].keep = 0;
-            }
-        }
-    printf("Translocations before filter: %d\n", n);
-    int n2 = 0;
-    for (int b = 0; b < n; b++) {
-        const ctx_row_t *q = &rw[b];
-        if (q->keep != 1) continue;
-        n2++;
-        char bnd[64];
-        const char *mn = (q->mchr >= 0 && q->mchr < n_t) ? lc[q->mchr] : "";
-        if (!vcf) { /* -f rows, GROM.c:22734 (g_sv_types[6] "CTX_F", [7] "CTX_R", GROM.c:867) */
-            fprintf(out, "%s\t%s\t%d\t%d\t%d\t%e\t%.1f\t%d\t%d\t%d\t%s\t%d\t%d\t%d\t%e\n", q->type == 6 ? "CTX_F" : "CTX_R",
-                    (q->chr >= 0 && q->chr < n_t) ? lc[q->chr] : "", q->pos, b, q->mateid, q->binom, q->ev, q->rd, q->conc,
-                    q->other, mn, q->mpos, q->rs, q->re, q->hez);
-            continue;
-        }
-        const int am = abs(q->mpos);
-        if (q->type == 6) snprintf(bnd, sizeof(bnd), q->mpos < 0 ? "N[%s:%d[" : "N]%s:%d]", mn, am);
-        else snprintf(bnd, sizeof(bnd), q->mpos < 0 ? "[%s:%d[N" : "]%s:%d]N", mn, am);
-        fprintf(out, "%s\t%d\t%d\tN\t%s\t.\t.\tSVTYPE=BND;MATEID=%d\tSPR:SEV:SRD:SCO:SOT:SFR:SLR:SHPR\t%e:%.1f:%d:%d:%d:%d:%d:%e\n",
-                (q->chr >= 0 && q->chr < n_t) ? lc[q->chr] : "", q->pos + 1, b, bnd, q->mateid, q->binom, q->ev, q->rd,
-                q->conc, q->other, q->rs + 1, q->re + 1, q->hez);
-    }
-    printf("Translocations after filter: %d\n", n2);
-    for (int a = 0; a < n_t; a++) free(lc[a]);
-    free(lc);
-    free(rw);
-}
-
-int grom_ctx_postpass(const char *raw, size_t raw_len, const char *const *target_names, int32_t n_targets,
-                      int32_t insert_max, int32_t lseq, grom_out *out) {
-    if (!out || n_targets < 0 || (n_targets > 0 && !target_names)) {
-        grom_set_last_error("grom_ctx_postpass: bad argument");
-        return GROM_E_ARG;
-    }
-    bam_hdr h;
-    memset(&h, 0, sizeof(h));
-    h.n_ref = n_targets;
-    h.ref_name = (char **)target_names;
-    char *buf = NULL;
-    size_t len = 0;
-    FILE *f = open_memstream(&buf, &len);
-    if (!f) { grom_set_last_error("grom_ctx_postpass: no memory"); return GROM_E_NOMEM; }
-    ctx_postpass(raw, raw_len, &h, insert_max, lseq, 1, f);
-    fclose(f);
-    if (out->ctx_len + len + 1 > out->ctx_cap) {
-        size_t nc = out->ctx_cap ? out->ctx_cap : 4096;
-        while (nc < out->ctx_len + len + 1) nc *= 2;
-        char *p = realloc(out->ctx, nc);
-        if (!p) { free(buf); grom_set_last_error("grom_ctx_postpass: no memory"); return GROM_E_NOMEM; }
-        out->ctx = p;
-        out->ctx_cap = nc;
-    }
-    memcpy(out->ctx + out->ctx_len, buf, len);
-    out->ctx_len += len;
-    out->ctx[out->ctx_len] = 0;
-    free(buf);
-    return GROM_OK;
+static void plan_release_dref(cli_state *S, chrom_plan *c) {
+    if (!c->d_ref) return;
+    pthread_mutex_lock(&S->fdev_mu);
+    if (S->fdev) grom_fasta_dev_release(S->fdev, c->d_ref);
+    c->d_ref = NULL;
+    pthread_mutex_unlock(&S->fdev_mu);
 }
 
 /* ---- one chromosome's scan, from either input path ----
@@ -411,10 +321,18 @@ typedef struct {
     char err[512];
 } grom_job;
 
-static void write_dumps(int slot, const chrom_plan *cp, const grom_chrom *ch, const grom_reads *host_rd,
-                        grom_stage *stage, const grom_params *P) {
-    /* test hook: per-base counters and caf depth, same files as the oracle's */
-    const char *dump = getenv("GROM_DUMP");
+static void dump_file(const char *dump, const char *chr, const char *ext, const void *p, size_t bytes) {
+    char path[4096];
+    snprintf(path, sizeof(path), "%s.%s.%s", dump, chr, ext);
+    FILE *f = fopen(path, "wb");
+    if (!f) return;
+    if (bytes) fwrite(p, 1, bytes, f);
+    fclose(f);
+}
+
+static void write_dumps(const char *dump, int slot, const chrom_plan *cp, const grom_chrom *ch,
+                        const grom_reads *host_rd, grom_stage *stage, const grom_params *P) {
+    /* test hook (GROM_DUMP): per-base counters and caf depth, same files as the oracle's */
     int32_t first = 0;
     int32_t lo = P->one_base_rd_len / 4 + 1;
     if (lo < 2 * P->insert_max_size + 1) lo = 2 * P->insert_max_size + 1;
@@ -424,20 +342,13 @@ static void write_dumps(int slot, const chrom_plan *cp, const grom_chrom *ch, co
     int rc = stage ? grom_debug_counts_staged(slot, stage, ch, &first, cnt, GROM_NCOUNT * n_eval, caf)
                    : grom_debug_counts(slot, ch, host_rd, &first, cnt, GROM_NCOUNT * n_eval, caf);
     if (rc == GROM_OK) {
-        char path[4096];
-        snprintf(path, sizeof(path), "%s.%s.cnt", dump, cp->name);
-        FILE *f = fopen(path, "wb");
-        if (f) { fwrite(cnt, sizeof(int32_t) * GROM_NCOUNT, n_eval, f); fclose(f); }
-        snprintf(path, sizeof(path), "%s.%s.caf", dump, cp->name);
-        f = fopen(path, "wb");
-        if (f) { fwrite(caf, sizeof(int32_t), 3 * cp->len, f); fclose(f); }
+        dump_file(dump, cp->name, "cnt", cnt, sizeof(int32_t) * GROM_NCOUNT * (size_t)n_eval);
+        dump_file(dump, cp->name, "caf", caf, sizeof(int32_t) * 3 * (size_t)cp->len);
         /* indel evidence of the same scan (row A7) */
         int64_t n_ind = grom_debug_indels(slot, NULL, 0);
         grom_indel_rec *ind = n_ind > 0 ? malloc(sizeof(grom_indel_rec) * n_ind) : NULL;
         if (n_ind >= 0 && (n_ind == 0 || (ind && grom_debug_indels(slot, ind, n_ind) == n_ind))) {
-            snprintf(path, sizeof(path), "%s.%s.ind", dump, cp->name);
-            f = fopen(path, "wb");
-            if (f) { if (n_ind) fwrite(ind, sizeof(grom_indel_rec), n_ind, f); fclose(f); }
+            dump_file(dump, cp->name, "ind", ind, sizeof(grom_indel_rec) * (size_t)n_ind);
         } else {
             fprintf(stderr, "grom: indel dump of %s failed: %s\n", cp->name, grom_last_error());
         }
@@ -446,11 +357,8 @@ static void write_dumps(int slot, const chrom_plan *cp, const grom_chrom *ch, co
          * GROM_SV_DEBUG is set) */
         int64_t n_sv = grom_debug_sv(slot, NULL, 0);
         grom_sv_rec *svr = n_sv > 0 ? malloc(sizeof(grom_sv_rec) * n_sv) : NULL;
-        if (n_sv >= 0 && (n_sv == 0 || (svr && grom_debug_sv(slot, svr, n_sv) == n_sv))) {
-            snprintf(path, sizeof(path), "%s.%s.sv", dump, cp->name);
-            f = fopen(path, "wb");
-            if (f) { if (n_sv) fwrite(svr, sizeof(grom_sv_rec), n_sv, f); fclose(f); }
-        }
+        if (n_sv >= 0 && (n_sv == 0 || (svr && grom_debug_sv(slot, svr, n_sv) == n_sv)))
+            dump_file(dump, cp->name, "sv", svr, sizeof(grom_sv_rec) * (size_t)n_sv);
         free(svr);
     } else {
         fprintf(stderr, "grom: counter dump of %s failed: %s\n", cp->name, grom_last_error());
@@ -459,12 +367,17 @@ static void write_dumps(int slot, const chrom_plan *cp, const grom_chrom *ch, co
     free(caf);
 }
 
-static int chrom_wanted(const char *name);
-
-static uint32_t chrom_seed(void) {
-    /* srand(time()) per chromosome, GROM.c:1584; GROM_SEED pins it */
-    const char *e = getenv("GROM_SEED");
-    return e ? (uint32_t)strtoul(e, NULL, 10) : (uint32_t)time(NULL);
+/* GROM_CHROMS=name[,name...]: scan and write only these chromosomes (one
+ * rank's share of a genome, bench.py --gpus N); the others keep their place
+ * in the plan, so each scanned chromosome gets the records the serial stream
+ * of a whole run would give it */
+static int chrom_wanted(const cli_state *S, const char *name) {
+    const char *w = S->env.chroms;
+    const size_t L = strlen(name);
+    if (!w || !*w) return 1;
+    for (const char *p = w; L && (p = strstr(p, name)) != NULL; p++) /* a whole entry of the list? */
+        if ((p == w || p[-1] == ',') && (p[L] == ',' || !p[L])) return 1;
+    return 0;
 }
 
 /* test hook (GROM_STAGE_DIGEST): the staged input of a chromosome, copied
@@ -472,9 +385,8 @@ static uint32_t chrom_seed(void) {
  * output against the host decoder's, tests/test_gpu_parity.py) */
 static void stage_digest_line(grom_stage *st, const grom_chrom *ch, int device) {
     grom_chrom dc;
-    grom_reads d, h;
+    grom_reads d, h = {0};
     if (grom_stage_view(st, ch, &dc, &d) != GROM_OK) return;
-    memset(&h, 0, sizeof(h));
     h.n = d.n;
     h.n_cigar_ops = d.n_cigar_ops;
     h.n_bases = d.n_bases;
@@ -515,50 +427,43 @@ static void job_stage_consumed(void *arg, grom_stage *st) {
     pd_release_stage(j->pd, st);
 }
 
-static int scan_job(int slot, grom_job *j, const grom_params *P, int verbose) {
+static int scan_job(int slot, grom_job *j, cli_state *S) {
+    const grom_params *P = &S->P;
+    const cli_settings *E = &S->env;
     chrom_plan *cp = j->cp;
     j->text = j->ctx_text = NULL;
     j->text_len = j->ctx_len = 0;
-    if (!chrom_wanted(cp->name)) return GROM_OK; /* serial path: another rank's chromosome */
-    grom_chrom ch;
-    memset(&ch, 0, sizeof(ch));
-    grom_reads rd;
-    memset(&rd, 0, sizeof(rd));
+    if (!chrom_wanted(S, cp->name)) return GROM_OK; /* serial path: another rank's chromosome */
+    grom_chrom ch = {0};
+    grom_reads rd = {0};
     int64_t n_reads;
     if (j->has_batch) {
         grom_batch *b = &j->batch;
         grom_batch_finish(b, P->one_base_rd_len / 4 + 1, P->overlap_mult, P->insert_max_size);
-        if (g_plan_only) {
-            grom_batch_view(b, &rd);
-            printf("plan %s tid=%d reads=%lld n_skip=%d p_last=%d lseq_tail=%d digest=%016llx\n", cp->name, cp->tid,
-                   (long long)b->n, b->n_skip, b->p_last, b->lseq_tail, (unsigned long long)pd_digest(&rd));
-            return GROM_OK;
-        }
         ch.lseq_tail = b->lseq_tail;
         ch.n_skip = b->n_skip;
         ch.p_last = b->p_last;
         grom_batch_view(b, &rd);
         n_reads = b->n;
     } else {
-        if (g_plan_only) { /* streamed plan-only (host tests): the decoder's host mirror */
-            pd_mirror_view(j->pd, j->k, &rd);
-            printf("plan %s tid=%d reads=%lld n_skip=%d p_last=%d lseq_tail=%d digest=%016llx\n", cp->name, cp->tid,
-                   (long long)j->facts.n_reads, j->facts.n_skip, j->facts.p_last, j->facts.lseq_tail,
-                   (unsigned long long)pd_digest(&rd));
-            return GROM_OK;
-        }
         ch.lseq_tail = j->facts.lseq_tail;
         ch.n_skip = j->facts.n_skip;
         ch.p_last = j->facts.p_last;
         n_reads = j->facts.n_reads;
+        if (E->plan_only) pd_mirror_view(j->pd, j->k, &rd); /* (host tests: the decoder's host mirror) */
+    }
+    if (E->plan_only) {
+        printf("plan %s tid=%d reads=%lld n_skip=%d p_last=%d lseq_tail=%d digest=%016llx\n", cp->name, cp->tid,
+               (long long)n_reads, ch.n_skip, ch.p_last, ch.lseq_tail, (unsigned long long)pd_digest(&rd));
+        return GROM_OK;
     }
     ch.ref = cp->ref;
     ch.len = cp->len;
     ch.name = cp->name;
     ch.tid = cp->tid;
     ch.cnv = cp->tid >= 0; /* detect_del_dup runs for a matched target, GROM.c:16633 */
-    ch.seed = chrom_seed();
-    if (!j->has_batch && getenv("GROM_STAGE_DIGEST")) stage_digest_line(j->stage, &ch, j->device);
+    ch.seed = E->has_seed ? E->seed : (uint32_t)time(NULL); /* srand(time()) per chromosome, GROM.c:1584 */
+    if (!j->has_batch && E->stage_digest) stage_digest_line(j->stage, &ch, j->device);
     grom_out out = {0};
     grom_stats st = {0};
     /* the pileup's input sizes (the verbose line) before the stage is given back */
@@ -571,7 +476,7 @@ static int scan_job(int slot, grom_job *j, const grom_params *P, int verbose) {
             n_b = dr.n_bases;
         }
         /* (GROM_DUMP reads the stage after the scan: it keeps it) */
-        grom_stage_on_consumed(j->stage, j->pd && !getenv("GROM_DUMP") ? job_stage_consumed : NULL, j);
+        grom_stage_on_consumed(j->stage, j->pd && !E->dump ? job_stage_consumed : NULL, j);
     }
     if (j->pd) pd_trace(j->pd, PD_EV_SCAN, j->k, 0);
     int rc = j->has_batch ? grom_scan_chrom(slot, &ch, &rd, &out, &st)
@@ -586,23 +491,21 @@ static int scan_job(int slot, grom_job *j, const grom_params *P, int verbose) {
     j->text_len = out.vcf_len;
     j->ctx_text = out.ctx; /* raw CTX rows for the translocation post-pass */
     j->ctx_len = out.ctx_len;
-    if (out.side_written && g_side_base) { /* -N: <results>.1000gen.<chr>, GROM.c:20246-20267 */
-        char *fn = malloc(strlen(g_side_base) + strlen(cp->name) + 16);
-        sprintf(fn, "%s.1000gen.%s", g_side_base, cp->name);
+    if (out.side_written && S->side_base) { /* -N: <results>.1000gen.<chr>, GROM.c:20246-20267 */
+        char fn[4096];
+        snprintf(fn, sizeof(fn), "%s.1000gen.%s", S->side_base, cp->name);
         FILE *f = fopen(fn, "w");
         if (!f) {
             printf("\nCould not open %s\n", fn);
-            free(fn);
             free(out.side);
             return GROM_E_ARG;
         }
         if (out.side_len) fwrite(out.side, 1, out.side_len, f);
         fclose(f);
-        free(fn);
     }
     free(out.side);
-    if (getenv("GROM_DUMP")) write_dumps(slot, cp, &ch, &rd, j->has_batch ? NULL : j->stage, P);
-    if (verbose) {
+    if (E->dump) write_dumps(E->dump, slot, cp, &ch, &rd, j->has_batch ? NULL : j->stage, P);
+    if (E->verbose) {
         /* the pileup kernel's launch and its inputs' sizes (bench.py's roofline) */
         printf("%s: %lld reads, %.3f ms on GPU (%.2f Mbases/s); pileup %.3f ms, cnv %.3f ms, cigar_ops %lld, "
                "bases %lld, len %ld\n", cp->name, (long long)n_reads, st.ms_total,
@@ -620,21 +523,15 @@ static int scan_job(int slot, grom_job *j, const grom_params *P, int verbose) {
  * counts) and scanned by one of that GPU's workers.  Rows are written in
  * chromosome order, so the VCF is the same bytes as a one-GPU run. */
 
-/* GROM_VCF_SEGS (a multi-GPU rank's run): where each chromosome's rows lie
- * in the VCF, "chromosome<TAB>offset<TAB>bytes" per line, so a merge of the
- * ranks' files copies byte ranges without reading the rows
- * (grom_amd.shard.merge_rank_outputs_parallel) */
-static textbuf g_vcf_segs;
-
 /* a finished chromosome: its VCF rows go out, its raw CTX rows are kept */
-static void take_rows(grom_job *j, FILE *vcf, textbuf *ctx_all) {
-    if (j->text_len && getenv("GROM_VCF_SEGS")) {
+static void take_rows(cli_state *S, grom_job *j, FILE *vcf, textbuf *ctx_all) {
+    if (j->text_len && S->env.vcf_segs) {
         const char *tab = memchr(j->text, '\t', j->text_len);
         char line[320];
         const int nl = tab ? (int)(tab - j->text) : 0;
         const int k = snprintf(line, sizeof(line), "%.*s\t%ld\t%zu\n", nl < 256 ? nl : 256, j->text, ftell(vcf),
                                (size_t)j->text_len);
-        if (k > 0) textbuf_add(&g_vcf_segs, line, (size_t)k);
+        if (k > 0) textbuf_add(&S->vcf_segs, line, (size_t)k);
     }
     if (j->text_len) fwrite(j->text, 1, j->text_len, vcf);
     free(j->text);
@@ -644,21 +541,28 @@ static void take_rows(grom_job *j, FILE *vcf, textbuf *ctx_all) {
     j->ctx_text = NULL;
 }
 
-typedef struct {
-    pthread_mutex_t mu;
-    pthread_cond_t cv;
-    grom_job *jobs;
-    int n_jobs, closing;
-    const grom_params *P;
-    int verbose;
-    const int *pos; /* pos[k]: the job of the k-th chromosome in BAM order (NULL: job k) */
-} grom_pool;
+typedef struct grom_pool grom_pool;
 
 typedef struct {
     grom_pool *pool;
+    pthread_t thr;
     int slot;   /* the worker's own library context (grom_ctx_init) */
     int device; /* its GPU */
 } grom_worker;
+
+struct grom_pool {
+    pthread_mutex_t mu;
+    pthread_cond_t cv;
+    grom_job *jobs; /* NULL: not started */
+    int n_jobs, closing;
+    cli_state *S;
+    const int *pos; /* pos[k]: the job of the k-th chromosome in BAM order (NULL: job k) */
+    grom_worker *workers;
+    /* the rows' way out, on the thread that hands the chromosomes over */
+    FILE *vcf;
+    textbuf ctx_all;
+    int next_write, status;
+};
 
 static void *grom_worker_main(void *arg) {
     grom_worker *w = (grom_worker *)arg;
@@ -682,11 +586,11 @@ static void *grom_worker_main(void *arg) {
         j->taken = 1;
         pthread_mutex_unlock(&pl->mu);
         /* contexts are independent: workers sharing a GPU scan concurrently */
-        int rc = scan_job(w->slot, j, pl->P, pl->verbose);
+        int rc = scan_job(w->slot, j, pl->S);
         if (rc != GROM_OK) snprintf(j->err, sizeof(j->err), "%s: %s", j->cp->name, grom_last_error());
         free(j->cp->ref);
         j->cp->ref = NULL;
-        plan_release_dref(j->cp);
+        plan_release_dref(pl->S, j->cp);
         if (j->has_batch) grom_batch_free(&j->batch);
         if (j->stage && j->pd && !j->stage_released) pd_release_stage(j->pd, j->stage);
         j->stage = NULL;
@@ -698,44 +602,6 @@ static void *grom_worker_main(void *arg) {
     }
     return NULL;
 }
-
-/* everything the two input paths share */
-typedef struct {
-    grom_params P;
-    const char *bam_name, *fasta_name, *out_name;
-    long max_chr_len;
-    double num_sd;
-    int device, verbose, n_dev;
-    bam_hdr hdr;
-    grom_fasta fa;
-    double *hez, *mq;
-    pthread_t tables_thr;
-    int tables_started;
-    chrom_plan *plan; /* candidates in BAM order (preliminary: before the length test) */
-    int n_cand;
-    char ctx_name[4096];
-    int wdev[64], n_work, n_init;
-    double t_cli0, t_cand; /* CLI start, candidates (FASTA lengths) done */
-    double t_load;         /* process start to the CLI's start (program and library loading) */
-    double t_scans, t_pdclose, t_outputs; /* scans done, decoder closed, outputs written */
-    double t_decclose;                     /* the decoder's host side closed */
-    pthread_t hip_thr;     /* HIP runtime start-up, beside the header/FASTA/index work */
-    int hip_started, hip_done;
-    /* -P n (1..256, GROM.c:21923-21927): every chromosome reads its own
-     * target's records (bam_fetch, GROM.c:21051-21064 and the -c children of
-     * GROM.c:549-599) -- pd_set_fetch_mode; GROM_P_SERIAL=1 keeps the serial
-     * stream's input (a one-process run's rows) on n GPUs */
-    int fetch;
-    /* -c chr,sub,start,end (GROM.c:21928-21930): one child of a -P n run --
-     * BAM target `one_chrom` alone, read through bam_fetch, its rows to
-     * OUT.<target>-<sub> and its raw CTX rows to OUT.<target>-<sub>.ctx, no
-     * header, no translocation post-pass (the parent concatenates and pairs,
-     * GROM.c:603-624, 22400), the insert statistics from <bam>.mean
-     * (GROM.c:22253-22257).  Whole chromosomes only (start 0, end at or past
-     * the chromosome's end: the children -P n forks without -R). */
-    int one_chrom, sub_child, sub_start, sub_end;
-    char part_name[4096];
-} cli_state;
 
 /* Peak device memory of this process (GROM_VERBOSE): the kernel driver's
  * per-process VRAM count (/sys/class/kfd/kfd/proc/<pid>/vram_<gpu>), sampled
@@ -770,12 +636,6 @@ static int64_t fp_kfd_bytes(void) {
     return any ? tot : -1;
 }
 
-static int64_t fp_sample(fp_sampler *F) {
-    if (F->kfd) return fp_kfd_bytes();
-    const int64_t fr = grom_device_mem_free(F->device);
-    return fr < 0 ? -1 : F->base - fr; /* base: free bytes at the start */
-}
-
 static void *fp_main(void *arg) {
     fp_sampler *F = (fp_sampler *)arg;
     F->kfd = fp_kfd_bytes() >= 0;
@@ -784,7 +644,8 @@ static void *fp_main(void *arg) {
     pthread_mutex_lock(&F->mu);
     while (!F->stop) {
         pthread_mutex_unlock(&F->mu);
-        const int64_t v = fp_sample(F);
+        int64_t v = F->kfd ? fp_kfd_bytes() : grom_device_mem_free(F->device);
+        if (!F->kfd && v >= 0) v = F->base - v; /* base: free bytes at the start */
         pthread_mutex_lock(&F->mu);
         if (v > F->peak) { F->peak = v; F->t_peak = clock_gettime_s() - t0; }
         struct timespec ts;
@@ -805,6 +666,7 @@ static void fp_start(fp_sampler *F, int device) {
     F->started = pthread_create(&F->thr, NULL, fp_main, F) == 0;
 }
 
+/* (since_start < 0: the sampler only ends, no line) */
 static void fp_stop(fp_sampler *F, double since_start) {
     if (!F->started) return;
     pthread_mutex_lock(&F->mu);
@@ -812,6 +674,8 @@ static void fp_stop(fp_sampler *F, double since_start) {
     pthread_cond_broadcast(&F->cv);
     pthread_mutex_unlock(&F->mu);
     pthread_join(F->thr, NULL);
+    F->started = 0;
+    if (since_start < 0) return;
     int64_t pk[GROM_DEVCAT_N + 1], nw = 0, ns = 0;
     double sw = 0, ss = 0;
     grom_dev_peaks(pk, NULL);
@@ -830,17 +694,20 @@ static void fp_stop(fp_sampler *F, double since_start) {
 }
 
 static void *hip_init_main(void *arg) {
-    const int device = *(const int *)arg;
+    const cli_state *S = (const cli_state *)arg;
     (void)grom_device_count();
-    if (getenv("GROM_NO_WARM") == NULL) dd_device_warm(device);
+    if (!S->env.no_warm) dd_device_warm(S->device);
     /* the device decoder's first context, made while the host reads the
      * FASTA lengths and the BAI (GROM_NO_CTX_PREPARE=1: made by the worker).
      * One context is prepared: with several decode workers per GPU
      * (GROM_DD_WORKERS > 1) the first to start takes it, the others make
      * their own */
-    const char *dd = getenv("GROM_DEVICE_DECODE"), *np = getenv("GROM_NO_CTX_PREPARE");
-    if (!(dd && atoi(dd) == 0) && !(np && atoi(np) == 1)) dd_ctx_prepare(device);
+    if (S->env.device_decode != 0 && !S->env.no_ctx_prepare) dd_ctx_prepare(S->device);
     return NULL;
+}
+
+static void hip_start(cli_state *S) {
+    S->hip_started = pthread_create(&S->hip_thr, NULL, hip_init_main, S) == 0;
 }
 
 static void hip_ready(cli_state *S) {
@@ -851,43 +718,44 @@ static void hip_ready(cli_state *S) {
     S->hip_started = 0;
 }
 
+/* the serial reader: after a fallback, or asked for (GROM_SERIAL_DECODE) */
+static int reads_serially(const cli_state *S) { return S->force_serial || S->env.serial_decode; }
+
+/* the host table and loader for -r.  `d`: the device loader gave up on the
+ * file (NULL: it was never opened); `why`: the library's reason goes with a refusal */
+static int fasta_host_fallback(cli_state *S, grom_fasta_dev **d, int why) {
+    if (d) {
+        fprintf(stderr, "grom: reading %s on the host\n", S->fasta_name);
+        grom_fasta_dev_close(*d);
+        grom_fasta_close(&S->fa);
+    }
+    if (grom_fasta_open_cached(&S->fa, S->fasta_name) == 0) return 0;
+    printf("\nCould not open %s\n", S->fasta_name);
+    if (why) printf("%s\n", grom_last_error());
+    return -1;
+}
+
 /* The -r file opened.  Plain text: the host table and loader, as ever
  * (GROM_FASTA_DEVICE=1: the device loader).  BGZF: the device loader
  * (GROM_FASTA_DEVICE=0, the serial reader and plan-only runs: inflated on the
  * host).  A gzip file that is not BGZF, with GROM_FASTA_GZIP=1: BGZF's routes
  * (else refused).  <fasta>.info is read and written either way; for a
- * compressed file its file_pos are offsets in the inflated text.  The device open waits for the
- * HIP start-up thread. */
-static int cli_fasta_open(cli_state *S, int force_serial) {
-    const int kind = grom_fasta_file_kind(S->fasta_name);
-    const char *fd = getenv("GROM_FASTA_DEVICE"), *ser = getenv("GROM_SERIAL_DECODE");
-    const int serial = force_serial || (ser && atoi(ser) > 0);
+ * compressed file its file_pos are offsets in the inflated text.  The device
+ * open waits for the HIP start-up thread. */
+static int cli_fasta_open(cli_state *S) {
+    const int kind = grom_fasta_file_kind(S->fasta_name), fd = S->env.fasta_device;
     const int gz = kind == 2 && grom_fasta_gzip_allowed(); /* a gzip file read as it is: BGZF's routes */
-    const int want = ((kind == 1 || gz) && !(fd && atoi(fd) == 0)) || (kind == 0 && fd && atoi(fd) == 1);
-    if ((kind == 2 && !gz) || !want || serial || g_plan_only) {
-        if (grom_fasta_open_cached(&S->fa, S->fasta_name) != 0) {
-            printf("\nCould not open %s\n", S->fasta_name);
-            if (kind == 2) printf("%s\n", grom_last_error());
-            return -1;
-        }
-        return 0;
-    }
-    S->hip_started = pthread_create(&S->hip_thr, NULL, hip_init_main, &S->device) == 0;
+    const int want = ((kind == 1 || gz) && fd != 0) || (kind == 0 && fd == 1);
+    if ((kind == 2 && !gz) || !want || reads_serially(S) || S->env.plan_only) return fasta_host_fallback(S, NULL, kind == 2);
+    hip_start(S);
     memset(&S->fa, 0, sizeof(S->fa));
     grom_fasta_info_load(&S->fa, S->fasta_name);
     const long kept = S->fa.n > 0 ? 0 : S->fa.mappable;
     hip_ready(S);
     grom_fasta_dev *d = NULL;
     const int orc = grom_fasta_dev_open(S->fasta_name, S->device, &d);
-    if (orc == GROM_FASTA_HOST_ONLY) { /* a gzip stream with a stretch too long for one lane */
-        fprintf(stderr, "grom: reading %s on the host\n", S->fasta_name);
-        grom_fasta_close(&S->fa);
-        if (grom_fasta_open_cached(&S->fa, S->fasta_name) != 0) {
-            printf("\nCould not open %s\n%s\n", S->fasta_name, grom_last_error());
-            return -1;
-        }
-        return 0;
-    }
+    /* "host only": a gzip stream with a stretch too long for one lane */
+    if (orc == GROM_FASTA_HOST_ONLY) return fasta_host_fallback(S, &d, 1);
     if (orc != 0) {
         printf("\nCould not open %s\n%s\n", S->fasta_name, grom_last_error());
         return -1;
@@ -916,19 +784,11 @@ static int cli_fasta_open(cli_state *S, int force_serial) {
             grom_fasta_info_save(&S->fa, S->fasta_name);
         }
     }
-    if (rc != 0) { /* "host only", or the device pass failed: the host reads the file */
+    if (rc != 0) { /* "host only", or the device pass failed */
         if (rc != GROM_FASTA_HOST_ONLY) fprintf(stderr, "grom: device FASTA loader: %s\n", grom_last_error());
-        fprintf(stderr, "grom: reading %s on the host\n", S->fasta_name);
-        grom_fasta_dev_close(d);
-        grom_fasta_close(&S->fa);
-        if (grom_fasta_open_cached(&S->fa, S->fasta_name) != 0) {
-            printf("\nCould not open %s\n", S->fasta_name);
-            return -1;
-        }
-        return 0;
+        return fasta_host_fallback(S, &d, 0);
     }
-    g_fdev = d;
-    g_fdev_device = S->device;
+    S->fdev = d;
     return 0;
 }
 
@@ -945,28 +805,33 @@ static void tables_join(cli_state *S) {
     S->tables_started = 0;
 }
 
-/* worker contexts: GROM_SCANS_PER_GPU (default 2) per GPU, so two
- * chromosomes are in flight on every GPU; GROM_WORKER_DEVICES=0,0,0 runs
- * three workers on device 0 (test hook) */
-static int setup_workers(cli_state *S) {
-    grom_params *P = &S->P;
-    if (getenv("GROM_DEVICES")) S->n_dev = atoi(getenv("GROM_DEVICES"));
+/* The run's device plan, derived here alone from the settings, -P and the
+ * free-memory query: the GPUs (GROM_DEVICES over -P n, at most those present
+ * from `device` on and at most 64), the scan contexts per GPU
+ * (GROM_SCANS_PER_GPU, default 2, so two chromosomes are in flight on every
+ * GPU), the worker -> GPU list and the streamed run's stages per GPU
+ * (GROM_STAGES).  GROM_WORKER_DEVICES=0,0,0 (test hook) runs three workers on
+ * device 0; a streamed run then has four stages, on the first listed device.
+ * `fit_hbm`: the contexts are about to be made (setup_workers), so their count
+ * is cut to what the free HBM holds now, after the stages took their share;
+ * the streamed run plans its stages and decoder before that, without it. */
+static int plan_devices(cli_state *S, int fit_hbm) {
+    const cli_settings *E = &S->env;
+    if (E->devices) S->n_dev = E->devices;
     if (S->n_dev < 1) S->n_dev = 1;
-    if (!g_plan_only && S->n_dev > 1) {
+    if (!E->plan_only && S->n_dev > 1) {
         int avail = grom_device_count();
         if (avail < 1) { fprintf(stderr, "grom: no GPU\n"); return -1; }
         if (S->n_dev > avail - S->device) S->n_dev = avail - S->device;
         if (S->n_dev < 1) S->n_dev = 1;
     }
-    int per_gpu = getenv("GROM_SCANS_PER_GPU") ? atoi(getenv("GROM_SCANS_PER_GPU")) : 2;
-    if (S->n_dev > 64) S->n_dev = 64;
-    if (per_gpu < 1) per_gpu = 1;
-    if (per_gpu * S->n_dev > 64) per_gpu = 64 / S->n_dev;
-    if (per_gpu < 1) per_gpu = 1;
+    if (S->n_dev > CLI_MAX_WORKERS) S->n_dev = CLI_MAX_WORKERS;
+    int per_gpu = E->scans_per_gpu;
+    if (per_gpu * S->n_dev > CLI_MAX_WORKERS) per_gpu = CLI_MAX_WORKERS / S->n_dev;
     /* a second context per GPU doubles the scan's device buffers: keep it
      * only when the free HBM holds per_gpu scans of the longest chromosome
      * (about 64 B per base at 30x) */
-    if (per_gpu > 1 && !g_plan_only) {
+    if (fit_hbm && per_gpu > 1 && !E->plan_only) {
         long longest = 0;
         for (int i = 0; i < S->fa.n; i++)
             if (S->fa.len[i] > longest) longest = S->fa.len[i];
@@ -980,37 +845,51 @@ static int setup_workers(cli_state *S) {
         }
     }
     S->n_work = S->n_dev * per_gpu;
-    for (int d = 0; d < 64; d++) S->wdev[d] = S->device + d % S->n_dev;
-    if (getenv("GROM_WORKER_DEVICES")) {
-        char *sdup = strdup(getenv("GROM_WORKER_DEVICES")), *tok = strtok(sdup, ",");
-        S->n_work = 0;
-        while (tok && S->n_work < 64) { S->wdev[S->n_work++] = atoi(tok); tok = strtok(NULL, ","); }
-        free(sdup);
+    for (int d = 0; d < CLI_MAX_WORKERS; d++) S->wdev[d] = S->device + d % S->n_dev;
+    if (E->n_worker_devices >= 0) {
+        S->n_work = E->n_worker_devices;
+        memcpy(S->wdev, E->worker_devices, sizeof(int) * (size_t)S->n_work);
         if (S->n_work < 1) { S->wdev[0] = S->device; S->n_work = 1; }
     }
+    return 0;
+}
+
+/* the scan workers' library contexts (they get their insert parameters later) */
+static int setup_workers(cli_state *S) {
+    if (plan_devices(S, 1)) return -1;
     tables_join(S);
     hip_ready(S);
     int rc = GROM_OK;
-    for (int d = 0; d < S->n_work && !g_plan_only && rc == GROM_OK; d++) {
-        rc = grom_ctx_init(d, S->wdev[d], P, S->hez, S->mq);
+    for (int d = 0; d < S->n_work && !S->env.plan_only && rc == GROM_OK; d++) {
+        rc = grom_ctx_init(d, S->wdev[d], &S->P, S->hez, S->mq);
         if (rc == GROM_OK) S->n_init = d + 1;
     }
     if (rc != GROM_OK) { fprintf(stderr, "grom: %s\n", grom_last_error()); return -1; }
     return 0;
 }
 
-/* set once the streamed run printed the insert lines: a serial rerun after
- * a late fallback (the index plan contradicted mid-file) does not print them
- * again, so stdout reads as one run */
-static __thread int t_insert_printed;
+/* The order chromosomes are best taken in: idx[0..n) sorted longest first,
+ * chromosomes of one length in their given order (a stable insertion sort) */
+static void longest_first(int *idx, int n, chrom_plan *const *p) {
+    for (int a = 1; a < n; a++)
+        for (int b = a; b > 0 && p[idx[b]]->len > p[idx[b - 1]]->len; b--) {
+            const int t = idx[b];
+            idx[b] = idx[b - 1];
+            idx[b - 1] = t;
+        }
+}
 
-static void print_insert(cli_state *S, int imean, int lseq, int imin, int imax, long mapped) {
-    const int quiet = t_insert_printed;
-    t_insert_printed = 1;
-    if (!quiet) printf("insert_min_size, insert_max_size %d %d\n", imin, imax);
+/* the insert lines and <bam>.mean (save_insert_mean, GROM.c:994-1008), or
+ * `given`: the statistics came from that file; a serial rerun prints nothing
+ * twice (insert_printed) */
+static void print_insert(cli_state *S, int given, int imean, int lseq, int imin, int imax, long mapped) {
+    const int quiet = *S->insert_printed && !given;
+    *S->insert_printed = 1;
     char mean_name[4096];
     snprintf(mean_name, sizeof(mean_name), "%s.mean", S->bam_name);
-    FILE *mf = fopen(mean_name, "w"); /* save_insert_mean, GROM.c:994-1008 */
+    if (given) printf("Loading insert_mean et al from %s\n", mean_name);
+    else if (!quiet) printf("insert_min_size, insert_max_size %d %d\n", imin, imax);
+    FILE *mf = given ? NULL : fopen(mean_name, "w");
     if (mf) {
         if (!quiet) printf("Saving insert_mean et al to %s\n", mean_name);
         fprintf(mf, "%d %d %d %d %ld\n", imean, lseq, imin, imax, mapped);
@@ -1027,43 +906,37 @@ static int passes_length(const cli_state *S, const chrom_plan *c) {
     const int32_t s0 = S->P.one_base_rd_len / 4 + 1;
     if (c->len > S->max_chr_len)
         printf("ERROR: Reference chromosome length exceeds maximum allowed chromosome size (%ld)\n", S->max_chr_len);
-    if (!(c->len > s0 + (long)S->P.overlap_mult * S->P.insert_max_size)) return 0;
-    if (!(c->len > 0 && c->len <= S->max_chr_len)) return 0;
-    return 1;
+    return c->len > s0 + (long)S->P.overlap_mult * S->P.insert_max_size && c->len > 0 && c->len <= S->max_chr_len;
+}
+
+/* the rows' file, under its header */
+static FILE *open_rows(cli_state *S) {
+    FILE *vcf = fopen(S->out_name, "w");
+    if (!vcf) { printf("Error opening file %s\n", S->out_name); return NULL; }
+    if (S->one_chrom < 0) { /* (-c: rows only, the parent wrote the header) */
+        if (S->P.vcf == 1) header(vcf, S->fasta_name, 0, S->env.filedate);
+        else tab_header(vcf, &S->P);
+    }
+    return vcf;
+}
+
+static void write_file(const char *name, const textbuf *t) {
+    FILE *f = fopen(name, "w");
+    if (!f) return;
+    if (t->len) fwrite(t->p, 1, t->len, f);
+    fclose(f);
 }
 
 static void finish_outputs(cli_state *S, textbuf *ctx_all) {
-    const char *segs = getenv("GROM_VCF_SEGS");
-    if (segs) {
-        FILE *f = fopen(segs, "w");
-        if (f) {
-            if (g_vcf_segs.len) fwrite(g_vcf_segs.p, 1, g_vcf_segs.len, f);
-            fclose(f);
-        }
-        free(g_vcf_segs.p);
-        memset(&g_vcf_segs, 0, sizeof(g_vcf_segs));
-    }
-    if (S->one_chrom >= 0) { /* -c: the raw CTX rows; the parent pairs them (GROM.c:22400) */
-        FILE *f = fopen(S->ctx_name, "w");
-        if (f) {
-            if (ctx_all->len) fwrite(ctx_all->p, 1, ctx_all->len, f);
-            fclose(f);
-        }
-        return;
-    }
-    const char *raw = getenv("GROM_CTX_RAW"); /* the raw CTX rows, for a merge of several ranks' runs */
-    if (raw) {
-        FILE *f = fopen(raw, "w");
-        if (f) {
-            if (ctx_all->len) fwrite(ctx_all->p, 1, ctx_all->len, f);
-            fclose(f);
-        }
-    }
+    if (S->env.vcf_segs) write_file(S->env.vcf_segs, &S->vcf_segs);
+    /* -c: the raw CTX rows; the parent pairs them (GROM.c:22400) */
+    if (S->one_chrom >= 0) { write_file(S->ctx_name, ctx_all); return; }
+    if (S->env.ctx_raw) write_file(S->env.ctx_raw, ctx_all); /* for a merge of several ranks' runs */
     /* CTX post-pass (GROM.c:22400-22770): pair the translocation rows of all
      * chromosomes with their mates and write them under the header */
     FILE *ctx = fopen(S->ctx_name, "w");
     if (ctx) {
-        if (S->P.vcf == 1) header(ctx, S->fasta_name, 1);
+        if (S->P.vcf == 1) header(ctx, S->fasta_name, 1, S->env.filedate);
         else /* the trimmed file's column header, GROM.c:22652-22700 */
             fputs("SV\tChromosome\tStart\tID\tMate ID\tBinom Prob (Start)\tCTX evidence\tRead Depth (High MapQ)\t"
                   "Concordant Pairs\tOther (Number of Non-Empty)\tMate Chr\tMate Pos\tRead Start\tRead End\t"
@@ -1074,43 +947,37 @@ static void finish_outputs(cli_state *S, textbuf *ctx_all) {
 }
 
 /* rows of finished jobs, in chromosome order (caller holds pool.mu) */
-static void drain_rows(grom_pool *pool, int *next_write, int upto, FILE *vcf, textbuf *ctx_all, int *status) {
-    while (*next_write < upto && pool->jobs[pool->pos ? pool->pos[*next_write] : *next_write].done) {
-        grom_job *j = &pool->jobs[pool->pos ? pool->pos[*next_write] : *next_write];
-        (*next_write)++;
+static void drain_rows(grom_pool *pool, int upto) {
+    while (pool->next_write < upto && pool->jobs[pool->pos ? pool->pos[pool->next_write] : pool->next_write].done) {
+        grom_job *j = &pool->jobs[pool->pos ? pool->pos[pool->next_write] : pool->next_write];
+        pool->next_write++;
         pthread_mutex_unlock(&pool->mu);
-        if (j->rc != GROM_OK) *status = 1;
-        take_rows(j, vcf, ctx_all);
+        if (j->rc != GROM_OK) pool->status = 1;
+        take_rows(pool->S, j, pool->vcf, &pool->ctx_all);
         pthread_mutex_lock(&pool->mu);
     }
 }
 
-static void pool_start(grom_pool *pool, cli_state *S, int n_jobs, grom_worker **workers, pthread_t **tids) {
-    memset(pool, 0, sizeof(*pool));
+static void pool_start(grom_pool *pool, cli_state *S, int n_jobs) {
     pthread_mutex_init(&pool->mu, NULL);
     pthread_cond_init(&pool->cv, NULL);
     pool->jobs = calloc(n_jobs > 0 ? n_jobs : 1, sizeof(grom_job));
     pool->n_jobs = n_jobs;
-    pool->P = &S->P;
-    pool->verbose = S->verbose;
-    *workers = calloc(S->n_work, sizeof(grom_worker));
-    *tids = calloc(S->n_work, sizeof(pthread_t));
+    pool->S = S;
+    pool->workers = calloc(S->n_work, sizeof(grom_worker));
     for (int d = 0; d < S->n_work; d++) {
-        (*workers)[d].pool = pool;
-        (*workers)[d].slot = d;
-        (*workers)[d].device = S->wdev[d];
-        pthread_create(&(*tids)[d], NULL, grom_worker_main, &(*workers)[d]);
+        pool->workers[d] = (grom_worker){.pool = pool, .slot = d, .device = S->wdev[d]};
+        pthread_create(&pool->workers[d].thr, NULL, grom_worker_main, &pool->workers[d]);
     }
 }
 
 /* close the pool: wait for every job, write the remaining rows */
-static void pool_finish(grom_pool *pool, cli_state *S, grom_worker *workers, pthread_t *tids, int *next_write,
-                        FILE *vcf, textbuf *ctx_all, int *status) {
+static void pool_finish(grom_pool *pool) {
     pthread_mutex_lock(&pool->mu);
     pool->closing = 1;
     pthread_cond_broadcast(&pool->cv);
     for (;;) {
-        drain_rows(pool, next_write, pool->n_jobs, vcf, ctx_all, status);
+        drain_rows(pool, pool->n_jobs);
         int busy = 0;
         for (int j = 0; j < pool->n_jobs; j++)
             if (pool->jobs[j].ready && !pool->jobs[j].done) busy = 1;
@@ -1118,152 +985,160 @@ static void pool_finish(grom_pool *pool, cli_state *S, grom_worker *workers, pth
         pthread_cond_wait(&pool->cv, &pool->mu);
     }
     pthread_mutex_unlock(&pool->mu);
-    for (int d = 0; d < S->n_work; d++) pthread_join(tids[d], NULL);
+    for (int d = 0; d < pool->S->n_work; d++) pthread_join(pool->workers[d].thr, NULL);
     for (int j = 0; j < pool->n_jobs; j++)
-        if (pool->jobs[j].ready && pool->jobs[j].rc != GROM_OK) { grom_set_last_error(pool->jobs[j].err); *status = 1; break; }
-    free(tids);
-    free(workers);
+        if (pool->jobs[j].ready && pool->jobs[j].rc != GROM_OK) { grom_set_last_error(pool->jobs[j].err); pool->status = 1; break; }
+    free(pool->workers);
     free(pool->jobs);
     pthread_mutex_destroy(&pool->mu);
     pthread_cond_destroy(&pool->cv);
 }
 
 /* ---------------- serial input: one pass over the record stream ---------------- */
-static int run_serial(cli_state *S) {
-    grom_params *P = &S->P;
+typedef struct {
+    cli_state *S;
     bgzf_reader br;
-    if (bgzf_open_read(&br, S->bam_name) != 0) return 1;
-    {
-        bam_hdr h2;
-        if (bam_read_header(&br, &h2) != 0) { bgzf_close_read(&br); return 1; }
-        bam_free_header(&h2);
+    int br_open;
+    chrom_plan **plan; /* the final plan: candidates that pass the length test */
+    int32_t *order;    /* their BAM targets */
+    int n_plan, cur;   /* `cur`: the chromosome whose records are being read */
+    grom_batch batch;
+    int batch_ended;   /* the record after the chromosome's last one was seen */
+    bam_rec rec;
+    grom_pool pool;
+} serial_run;
+
+/* the BAM opened at its first record; `threads`: its blocks inflate on so many threads */
+static int serial_open(serial_run *R, const int *threads) {
+    if (bgzf_open_read(&R->br, R->S->bam_name) != 0) return 1;
+    R->br_open = 1;
+    if (threads && bgzf_set_threads(&R->br, *threads) != 0) return 1;
+    bam_hdr h2;
+    if (bam_read_header(&R->br, &h2) != 0) return 1;
+    bam_free_header(&h2);
+    return 0;
+}
+
+static void serial_batch_init(serial_run *R) {
+    if (R->cur >= R->n_plan) return;
+    grom_batch_init(&R->batch, R->order[R->cur], R->S->P.read_name_len);
+    grom_batch_set_sv(&R->batch, R->plan[R->cur]->target, R->S->P.splitread);
+    R->batch_ended = 0;
+}
+
+/* hand chromosome `cur` (its batch complete) to the workers; at most one
+ * decoded chromosome waits beyond those being scanned */
+static void serial_submit(serial_run *R) {
+    grom_pool *pool = &R->pool;
+    chrom_plan *c = R->plan[R->cur];
+    c->ref = malloc(c->len + 1);
+    grom_fasta_load(&R->S->fa, c->fasta_idx, c->ref, c->len);
+    pthread_mutex_lock(&pool->mu);
+    grom_job *j = &pool->jobs[R->cur];
+    j->cp = c;
+    j->batch = R->batch;
+    j->has_batch = 1;
+    j->device = -1;
+    j->ready = 1;
+    pthread_cond_broadcast(&pool->cv);
+    for (;;) {
+        drain_rows(pool, R->cur + 1);
+        if (R->cur + 1 - pool->next_write < R->S->n_work + 1) break;
+        pthread_cond_wait(&pool->cv, &pool->mu);
     }
-    /* insert-size pre-pass on the first records (GROM.c:22255) */
+    pthread_mutex_unlock(&pool->mu);
+    R->cur++;
+    serial_batch_init(R);
+}
+
+/* the insert-size pre-pass on the first records (GROM.c:22255), the scan
+ * contexts, and the final plan */
+static int serial_prepare(serial_run *R) {
+    cli_state *S = R->S;
+    if (serial_open(R, NULL)) return 1;
     int lseq = 0, imin = 0, imax = 0;
     long mapped = 0;
-    int imean = grom_insert_stats(&br, grom_prob2(S->num_sd), &lseq, &imin, &imax, &mapped, P->min_mapq);
-    bgzf_close_read(&br);
+    int imean = grom_insert_stats(&R->br, grom_prob2(S->num_sd), &lseq, &imin, &imax, &mapped, S->P.min_mapq);
+    bgzf_close_read(&R->br);
+    R->br_open = 0;
     if (imean < 0) { printf("ERROR: no reads to estimate the insert size from\n"); return 1; }
-    print_insert(S, imean, lseq, imin, imax, mapped);
+    print_insert(S, 0, imean, lseq, imin, imax, mapped);
     if (setup_workers(S)) return 1;
-    /* the final plan: candidates that pass the length test */
-    const int32_t s0 = P->one_base_rd_len / 4 + 1;
-    chrom_plan **plan = calloc(S->n_cand > 0 ? S->n_cand : 1, sizeof(chrom_plan *));
-    int32_t *order = calloc(S->n_cand > 0 ? S->n_cand : 1, sizeof(int32_t));
-    int n_plan = 0;
+    R->plan = calloc(S->n_cand > 0 ? S->n_cand : 1, sizeof(chrom_plan *));
+    R->order = calloc(S->n_cand > 0 ? S->n_cand : 1, sizeof(int32_t));
     for (int c = 0; c < S->n_cand; c++)
         if (passes_length(S, &S->plan[c])) {
-            order[n_plan] = S->plan[c].tid;
-            plan[n_plan++] = &S->plan[c];
+            R->order[R->n_plan] = S->plan[c].tid;
+            R->plan[R->n_plan++] = &S->plan[c];
         }
-    FILE *vcf = fopen(S->out_name, "w");
-    if (!vcf) { printf("Error opening file %s\n", S->out_name); free(plan); free(order); return 1; }
-    if (S->one_chrom < 0) { /* (-c: rows only, the parent wrote the header) */
-        if (P->vcf == 1) header(vcf, S->fasta_name, 0);
-        else tab_header(vcf, P);
-    }
-    /* one serial pass over the records, split per chromosome (stream.h);
-     * finished chromosomes go to the GPU workers, rows are written in order */
-    if (bgzf_open_read(&br, S->bam_name) != 0) { fclose(vcf); free(plan); free(order); return 1; }
-    {
-        /* BGZF blocks inflate on GROM_DECODE_THREADS threads (default 4) while
-         * this thread parses records in order (htslib's bgzf_mt) */
-        const char *dt = getenv("GROM_DECODE_THREADS");
-        const int n_dec = dt ? atoi(dt) : 4;
-        if (bgzf_set_threads(&br, n_dec) != 0) { bgzf_close_read(&br); fclose(vcf); free(plan); free(order); return 1; }
-    }
-    {
-        bam_hdr h2;
-        if (bam_read_header(&br, &h2) != 0) { bgzf_close_read(&br); fclose(vcf); free(plan); free(order); return 1; }
-        bam_free_header(&h2);
-    }
+    return 0;
+}
+
+/* One serial pass over the records, split per chromosome (stream.h); finished
+ * chromosomes go to the GPU workers, rows are written in order.  BGZF blocks
+ * inflate on GROM_DECODE_THREADS threads (default 4) while this thread parses
+ * records in order (htslib's bgzf_mt) */
+static void serial_read(serial_run *R) {
+    const cli_state *S = R->S;
+    const int32_t s0 = S->P.one_base_rd_len / 4 + 1;
+    bam_rec *rec = &R->rec;
     grom_planner pl;
-    grom_planner_init(&pl, order, n_plan);
-    grom_batch batch;
-    int cur = 0;
-    int batch_ended = 0; /* the record after the chromosome's last one was seen */
-    if (n_plan > 0) {
-        grom_batch_init(&batch, order[0], P->read_name_len);
-        grom_batch_set_sv(&batch, plan[0]->target, P->splitread);
-    }
-    bam_rec rec;
-    memset(&rec, 0, sizeof(rec));
-    int status = 0, next_write = 0;
-    grom_pool pool;
-    grom_worker *workers;
-    pthread_t *tids;
-    pool_start(&pool, S, n_plan, &workers, &tids);
-    textbuf ctx_all = {0};
-    /* hand chromosome `cur` (its batch complete) to the workers; at most one
-     * decoded chromosome waits beyond those being scanned */
-    #define SUBMIT_CUR()                                                                           \
-        do {                                                                                       \
-            plan[cur]->ref = malloc(plan[cur]->len + 1);                                           \
-            grom_fasta_load(&S->fa, plan[cur]->fasta_idx, plan[cur]->ref, plan[cur]->len);         \
-            pthread_mutex_lock(&pool.mu);                                                          \
-            pool.jobs[cur].cp = plan[cur];                                                         \
-            pool.jobs[cur].batch = batch;                                                          \
-            pool.jobs[cur].has_batch = 1;                                                          \
-            pool.jobs[cur].device = -1;                                                            \
-            pool.jobs[cur].ready = 1;                                                              \
-            pthread_cond_broadcast(&pool.cv);                                                      \
-            for (;;) {                                                                             \
-                drain_rows(&pool, &next_write, cur + 1, vcf, &ctx_all, &status);                   \
-                if (cur + 1 - next_write < S->n_work + 1) break;                                   \
-                pthread_cond_wait(&pool.cv, &pool.mu);                                             \
-            }                                                                                      \
-            pthread_mutex_unlock(&pool.mu);                                                        \
-            cur++;                                                                                 \
-            if (cur < n_plan) {                                                                    \
-                grom_batch_init(&batch, order[cur], P->read_name_len);                             \
-                grom_batch_set_sv(&batch, plan[cur]->target, P->splitread);                        \
-                batch_ended = 0;                                                                   \
-            }                                                                                      \
-        } while (0)
-    while (S->fetch && cur < n_plan && bam_read_rec(&br, &rec) > 0) {
+    grom_planner_init(&pl, R->order, R->n_plan);
+    serial_batch_init(R);
+    while (S->fetch && R->cur < R->n_plan && bam_read_rec(&R->br, rec) > 0) {
         /* -P: chromosome `cur` is given its own target's placed records
          * (bam_fetch over [0, MAX_REGION), GROM.c:320) and its stream ends at
          * its last one; a record of a later plan chromosome completes every
          * chromosome before it.  The file is coordinate-sorted (bam_fetch's
          * precondition): a record of an earlier target cannot follow. */
-        if (rec.pos < 0 || rec.pos >= 300000000) continue;
+        if (rec->pos < 0 || rec->pos >= 300000000) continue;
         int k = -1;
-        for (int j = cur; j < n_plan && k < 0; j++)
-            if (order[j] == rec.tid) k = j;
+        for (int j = R->cur; j < R->n_plan && k < 0; j++)
+            if (R->order[j] == rec->tid) k = j;
         if (k < 0) {
-            for (int j = 0; j < cur; j++)
-                if (order[j] == rec.tid) {
-                    fprintf(stderr, "grom: -P needs a coordinate-sorted BAM (target %d after a later one)\n", rec.tid);
-                    status = 1;
+            for (int j = 0; j < R->cur; j++)
+                if (R->order[j] == rec->tid) {
+                    fprintf(stderr, "grom: -P needs a coordinate-sorted BAM (target %d after a later one)\n", rec->tid);
+                    R->pool.status = 1;
                 }
-            if (status) break;
+            if (R->pool.status) break;
             continue;
         }
-        while (cur < k) SUBMIT_CUR();
-        grom_batch_add(&batch, &rec, s0);
+        while (R->cur < k) serial_submit(R);
+        grom_batch_add(&R->batch, rec, s0);
     }
-    while (!S->fetch && cur < n_plan && bam_read_rec(&br, &rec) > 0) {
+    while (!S->fetch && R->cur < R->n_plan && bam_read_rec(&R->br, rec) > 0) {
         /* cdp_lseq after the chromosome: the l_qseq of the record that ended
          * it (the R-side edge tests of its last bases read it, GROM.c:12047) */
-        if (!batch_ended && batch.n_seen > 0 && rec.tid != order[cur]) {
-            grom_batch_end_record(&batch, &rec);
-            batch_ended = 1;
+        if (!R->batch_ended && R->batch.n_seen > 0 && rec->tid != R->order[R->cur]) {
+            grom_batch_end_record(&R->batch, rec);
+            R->batch_ended = 1;
         }
-        int k = grom_planner_feed(&pl, rec.tid);
-        while (cur < n_plan && pl.k > cur) SUBMIT_CUR(); /* chromosome `cur` is complete */
-        if (k >= 0 && k == cur) grom_batch_add(&batch, &rec, s0);
+        int k = grom_planner_feed(&pl, rec->tid);
+        while (R->cur < R->n_plan && pl.k > R->cur) serial_submit(R); /* chromosome `cur` is complete */
+        if (k >= 0 && k == R->cur) grom_batch_add(&R->batch, rec, s0);
     }
     /* end of file: the chromosome being read and every later one */
-    while (cur < n_plan) SUBMIT_CUR();
-    #undef SUBMIT_CUR
-    pool_finish(&pool, S, workers, tids, &next_write, vcf, &ctx_all, &status);
-    bam_free_rec(&rec);
-    bgzf_close_read(&br);
-    fclose(vcf);
-    finish_outputs(S, &ctx_all);
-    free(ctx_all.p);
-    free(plan);
-    free(order);
+    while (R->cur < R->n_plan) serial_submit(R);
+}
+
+static int run_serial(cli_state *S) {
+    serial_run R = {.S = S};
+    const int n_dec = S->env.has_decode_threads ? S->env.decode_threads : 4;
+    int status = 1;
+    if (!serial_prepare(&R) && (R.pool.vcf = open_rows(S)) != NULL && !serial_open(&R, &n_dec)) {
+        pool_start(&R.pool, S, R.n_plan);
+        serial_read(&R);
+        pool_finish(&R.pool);
+        status = R.pool.status;
+    }
+    bam_free_rec(&R.rec);
+    if (R.br_open) bgzf_close_read(&R.br);
+    if (R.pool.vcf) fclose(R.pool.vcf);
+    if (R.pool.S) finish_outputs(S, &R.pool.ctx_all); /* (only a run whose pool started writes them) */
+    free(R.pool.ctx_all.p);
+    free(R.plan);
+    free(R.order);
     return status;
 }
 
@@ -1277,10 +1152,10 @@ typedef struct {
     int loaded, consumed, stop; /* refs loaded (a prefix of the plan) ahead of the consumer, at most `ahead` */
     int ahead;
     int next;         /* the next chromosome a loader thread takes */
-    char *done;       /* per chromosome: its reference is loaded */
+    char *done;       /* per chromosome: its reference is loaded (NULL: the feed was never set up) */
+    pthread_t thr[8]; /* GROM_FASTA_THREADS' upper bound */
+    int n_thr;
 } fasta_feed;
-
-#define FASTA_THREADS_MAX 8
 
 /* A chromosome's reference buffer: 2 MB aligned and advised for huge pages,
  * so the first touch of a 250 MB chromosome is ~125 faults instead of ~61 k
@@ -1323,14 +1198,14 @@ static void *fasta_main(void *arg) {
         if (stop) break;
         chrom_plan *c = F->plan[k];
         c->ref = ref_alloc(c->len);
-        if (c->ref && g_fdev) {
+        if (c->ref && F->S->fdev) {
             /* the device loader: the bytes stay in HBM for the stage and come back for the host's SV rows */
-            pthread_mutex_lock(&g_fdev_mu);
-            const int64_t r = grom_fasta_dev_load(g_fdev, c->fasta_idx, c->ref, c->len, &c->d_ref);
-            pthread_mutex_unlock(&g_fdev_mu);
+            pthread_mutex_lock(&F->S->fdev_mu);
+            const int64_t r = grom_fasta_dev_load(F->S->fdev, c->fasta_idx, c->ref, c->len, &c->d_ref);
+            pthread_mutex_unlock(&F->S->fdev_mu);
             if (r != c->len) {
                 if (r != GROM_FASTA_HOST_ONLY) fprintf(stderr, "grom: device FASTA loader: %s; reading %s on the host\n", grom_last_error(), c->name);
-                plan_release_dref(c);
+                plan_release_dref(F->S, c);
                 cli_fasta_host_load(F->S, c->fasta_idx, c->ref, c->len);
             }
         } else if (c->ref && grom_fasta_load_at(&F->S->fa, c->fasta_idx, c->ref, c->len) < 0) {
@@ -1367,409 +1242,379 @@ static int host_cpus(void) {
     return ncpu < 1 ? 1 : (int)ncpu;
 }
 
-/* GROM_CHROMS=name[,name...]: scan and write only these chromosomes (one
- * rank's share of a genome, bench.py --gpus N); the others keep their place
- * in the plan, so each scanned chromosome gets the records the serial stream
- * of a whole run would give it */
-static int chrom_wanted(const char *name) {
-    const char *w = getenv("GROM_CHROMS");
-    if (!w || !*w) return 1;
-    const size_t L = strlen(name);
-    for (const char *p = w; *p;) {
-        const char *e = strchr(p, ',');
-        const size_t n = e ? (size_t)(e - p) : strlen(p);
-        if (n == L && strncmp(p, name, n) == 0) return 1;
-        if (!e) break;
-        p = e + 1;
-    }
-    return 0;
-}
-
-/* GROM_CLI_PROCESS=1 (opt-in, for a `grom` process; never for in-process
- * callers such as the Python binding): the process ends once a streamed
- * run's outputs are written */
-static int cli_process_exit(void) {
-    const char *e = getenv("GROM_CLI_PROCESS");
-    return e && atoi(e) == 1;
-}
-
 static void *stage_free_main(void *arg) {
     grom_stage_free((grom_stage *)arg);
     return NULL;
 }
 
-static int run_streamed(cli_state *S) {
-    grom_params *P = &S->P;
-    const double t_start = clock_gettime_s();
-    /* the preliminary plan: every candidate (the length test needs the
-     * insert size, which the same decode measures) */
-    pd_chrom_in *cin = calloc(S->n_cand > 0 ? S->n_cand : 1, sizeof(pd_chrom_in));
+/* a streamed run: what its phases share, and what streamed_close releases */
+typedef struct {
+    cli_state *S;
+    pd_session *pd;
+    int *dev_of; /* candidate -> the GPU its stage and scan are on */
+    grom_stage *stages[256];
+    int n_stages;
+    /* insert statistics read from <bam>.mean (`given`), else measured */
+    int given, imean, lseq, imin, imax;
+    long mapped;
+    int status, fallback; /* the run failed; the serial reader has to take over */
+    /* the final plan: wanted candidates that pass the length test, in BAM
+     * order; pidx[k]: the k-th one's candidate */
+    int *keep, *pidx, n_plan;
+    chrom_plan **plan;
+    /* the queue: the order chromosomes are taken in; qpos[k]: where the k-th of the plan stands in it */
+    int *qord, *qpos;
+    chrom_plan **qplan;
+    fasta_feed F;
+    grom_pool pool;
+    double t_start, t_started, t_stats, t_ctx, t_loop;
+} streamed_run;
+
+/* longest processing time first over the chromosome lengths: every candidate's GPU */
+static void assign_devices(const cli_state *S, int *dev_of) {
+    const int n = S->n_cand;
+    double load[CLI_MAX_WORKERS] = {0};
+    int *idx = malloc(sizeof(int) * (n > 0 ? n : 1));
+    chrom_plan **all = calloc(n > 0 ? n : 1, sizeof(chrom_plan *));
+    for (int c = 0; c < n; c++) { idx[c] = c; all[c] = &S->plan[c]; }
+    longest_first(idx, n, all);
+    for (int a = 0; a < n; a++) {
+        int best = 0;
+        for (int d = 1; d < S->n_dev; d++)
+            if (load[d] < load[best]) best = d;
+        dev_of[idx[a]] = S->device + best;
+        load[best] += (double)all[idx[a]]->len;
+    }
+    /* (GROM_WORKER_DEVICES, test hook: every chromosome on the stages' one device) */
+    for (int c = 0; c < n && S->env.n_worker_devices >= 0; c++) dev_of[c] = S->wdev[0];
+    free(idx);
+    free(all);
+}
+
+/* phase 1: the decoder opened over the preliminary plan (every candidate: the
+ * length test needs the insert size, which the same decode measures), the
+ * stages made and the decode started */
+static int streamed_open(streamed_run *R) {
+    cli_state *S = R->S;
+    const cli_settings *E = &S->env;
+    const int n1 = S->n_cand > 0 ? S->n_cand : 1;
+    pd_chrom_in *cin = calloc(n1, sizeof(pd_chrom_in));
     for (int c = 0; c < S->n_cand; c++) {
         cin[c].tid = S->plan[c].tid;
         cin[c].target_name = S->plan[c].target;
         cin[c].len = S->plan[c].len;
     }
-    const char *dt = getenv("GROM_DECODE_THREADS");
     /* the host decoder's threads (GROM_DEVICE_DECODE=0 and plan-only runs):
      * the CPU share, at most 32 (its piece window grows with the count) */
-    int n_thr = dt ? atoi(dt) : (host_cpus() < 32 ? host_cpus() : 32);
+    int n_thr = E->has_decode_threads ? E->decode_threads : (host_cpus() < 32 ? host_cpus() : 32);
     if (n_thr < 1) n_thr = 1;
     char why[256] = "";
-    pd_session *pd = pd_open(S->bam_name, &S->hdr, cin, S->n_cand, P->splitread, P->read_name_len, n_thr, why,
-                             (int)sizeof(why));
+    R->pd = pd_open(S->bam_name, &S->hdr, cin, S->n_cand, S->P.splitread, S->P.read_name_len, n_thr, why,
+                    (int)sizeof(why));
     free(cin);
-    if (!pd) {
-        if (S->verbose) printf("streamed decode not used: %s\n", why);
+    if (!R->pd) {
+        if (E->verbose) printf("streamed decode not used: %s\n", why);
         return CLI_FALLBACK;
     }
     /* GPUs: contexts need the insert statistics, stages do not */
     hip_ready(S);
-    if (getenv("GROM_DEVICES")) S->n_dev = atoi(getenv("GROM_DEVICES"));
-    if (S->n_dev < 1) S->n_dev = 1;
-    if (!g_plan_only && S->n_dev > 1) {
-        int avail = grom_device_count();
-        if (avail < 1) { fprintf(stderr, "grom: no GPU\n"); pd_close(pd); return 1; }
-        if (S->n_dev > avail - S->device) S->n_dev = avail - S->device;
-        if (S->n_dev < 1) S->n_dev = 1;
-    }
-    int *dev_of = calloc(S->n_cand > 0 ? S->n_cand : 1, sizeof(int));
-    {
-        /* longest processing time first over the chromosome lengths */
-        double load[64] = {0};
-        int *idx = malloc(sizeof(int) * (S->n_cand > 0 ? S->n_cand : 1));
-        for (int c = 0; c < S->n_cand; c++) idx[c] = c;
-        for (int a = 1; a < S->n_cand; a++) /* insertion sort, longest first, stable */
-            for (int b = a; b > 0 && S->plan[idx[b]].len > S->plan[idx[b - 1]].len; b--) {
-                int t = idx[b]; idx[b] = idx[b - 1]; idx[b - 1] = t;
-            }
-        for (int a = 0; a < S->n_cand; a++) {
-            int best = 0;
-            for (int d = 1; d < S->n_dev; d++)
-                if (load[d] < load[best]) best = d;
-            dev_of[idx[a]] = S->device + best;
-            load[best] += (double)S->plan[idx[a]].len;
-        }
-        free(idx);
-    }
-    const char *wd = getenv("GROM_WORKER_DEVICES");
-    if (wd) { /* test hook: every stage on the first listed device */
-        for (int c = 0; c < S->n_cand; c++) dev_of[c] = atoi(wd);
-    }
-    grom_stage *stages[256];
-    int n_stages = 0;
-    if (!g_plan_only) {
-        int per_gpu = getenv("GROM_SCANS_PER_GPU") ? atoi(getenv("GROM_SCANS_PER_GPU")) : 2;
-        if (per_gpu < 1) per_gpu = 1;
-        /* one stage per scan: a scan gives its stage back before its CNV
-         * path (grom_stage_on_consumed), so the next chromosome decodes into
-         * it while the CNV path runs.  A third stage (GROM_STAGES=3, the
-         * round-4/5 default) let the decode run one chromosome further ahead
-         * for 15.5 GB more at 30x, and the whole run was no faster
-         * (profiles/r05r: 4.03-4.04 s against 4.00-4.12 s) */
-        int n_st = getenv("GROM_STAGES") ? atoi(getenv("GROM_STAGES")) : per_gpu;
-        if (n_st < 1) n_st = 1;
-        for (int d = 0; d < S->n_dev && !wd; d++)
-            for (int k = 0; k < n_st && n_stages < 256; k++) {
-                grom_stage *st = grom_stage_new(S->device + d);
-                if (!st) break;
-                stages[n_stages++] = st;
-                pd_add_stage(pd, st, S->device + d);
-            }
-        for (int k = 0; wd && k < 4; k++) {
-            grom_stage *st = grom_stage_new(atoi(wd));
+    if (plan_devices(S, 0)) return 1;
+    R->dev_of = calloc(5 * (size_t)n1, sizeof(int)); /* with keep, pidx, qord and qpos behind it */
+    R->plan = calloc(2 * (size_t)n1, sizeof(chrom_plan *)); /* with qplan */
+    assign_devices(S, R->dev_of);
+    /* one stage per scan: a scan gives its stage back before its CNV path
+     * (grom_stage_on_consumed), so the next chromosome decodes into it while
+     * the CNV path runs.  A third stage (GROM_STAGES=3, the round-4/5
+     * default) let the decode run one chromosome further ahead for 15.5 GB
+     * more at 30x, and the whole run was no faster (profiles/r05r: 4.03-4.04 s
+     * against 4.00-4.12 s) */
+    const int hook = E->n_worker_devices >= 0; /* GROM_WORKER_DEVICES: four stages, on the first worker's device */
+    const int dev0 = hook ? S->wdev[0] : S->device, gpus = hook ? 1 : S->n_dev, per_gpu = hook ? 4 : E->stages;
+    for (int d = 0; d < gpus && !E->plan_only; d++)
+        for (int k = 0; k < per_gpu && R->n_stages < 256; k++) {
+            grom_stage *st = grom_stage_new(dev0 + d);
             if (!st) break;
-            stages[n_stages++] = st;
-            pd_add_stage(pd, st, atoi(wd));
+            R->stages[R->n_stages++] = st;
+            pd_add_stage(R->pd, st, dev0 + d);
         }
-    }
     /* a share of a multi-process run (GROM_CHROMS, bench.py --gpus N) reads
      * the insert statistics from <bam>.mean as the reference's -c children do
      * (load_insert_mean, GROM.c:1011-1026, 22253-22257) */
-    int given = 0, g_mean = 0, g_lseq = 0, g_min = 0, g_max = 0;
-    long g_mapped = 0;
-    char mean_name[4096];
-    snprintf(mean_name, sizeof(mean_name), "%s.mean", S->bam_name);
-    if ((getenv("GROM_CHROMS") || S->one_chrom >= 0) && !g_plan_only) {
+    if ((E->chroms || S->one_chrom >= 0) && !E->plan_only) {
+        char mean_name[4096];
+        snprintf(mean_name, sizeof(mean_name), "%s.mean", S->bam_name);
         FILE *mf = fopen(mean_name, "r");
         if (mf) {
-            given = fscanf(mf, "%d %d %d %d %ld", &g_mean, &g_lseq, &g_min, &g_max, &g_mapped) == 5 && g_mean > 0;
+            R->given = fscanf(mf, "%d %d %d %d %ld", &R->imean, &R->lseq, &R->imin, &R->imax, &R->mapped) == 5 &&
+                       R->imean > 0;
             fclose(mf);
         }
-        if (given) pd_stats_given(pd);
+        if (R->given) pd_stats_given(R->pd);
     }
-    if (S->fetch) pd_set_fetch_mode(pd, 1);
-    if (getenv("GROM_CHROMS")) {
-        int *want = calloc(S->n_cand > 0 ? S->n_cand : 1, sizeof(int));
-        for (int c = 0; c < S->n_cand; c++) want[c] = chrom_wanted(S->plan[c].name);
-        pd_set_wanted(pd, want);
+    if (S->fetch) pd_set_fetch_mode(R->pd, 1);
+    if (E->chroms) {
+        int *want = calloc(n1, sizeof(int));
+        for (int c = 0; c < S->n_cand; c++) want[c] = chrom_wanted(S, S->plan[c].name);
+        pd_set_wanted(R->pd, want);
         free(want);
     }
     /* BAM decode on the GPUs (ddecode.hip) by default; the host decoder
      * threads with GROM_DEVICE_DECODE=0 (plan-only runs always use them) */
-    {
-        const char *dd = getenv("GROM_DEVICE_DECODE");
-        pd_set_device_mode(pd, !g_plan_only && !(dd && atoi(dd) == 0));
-    }
-    if (pd_start(pd, P->min_mapq, S->n_dev, dev_of, g_plan_only)) {
-        fprintf(stderr, "grom: %s\n", pd_error(pd));
-        pd_close(pd);
-        for (int i = 0; i < n_stages; i++) grom_stage_free(stages[i]);
-        free(dev_of);
+    pd_set_device_mode(R->pd, !E->plan_only && E->device_decode != 0);
+    if (pd_start(R->pd, S->P.min_mapq, S->n_dev, R->dev_of, E->plan_only)) {
+        fprintf(stderr, "grom: %s\n", pd_error(R->pd));
         return 1;
     }
-    int status = 0;
-    int lseq = 0, imin = 0, imax = 0;
-    long mapped = 0;
-    const double t_started = clock_gettime_s();
-    /* the scan contexts while the head of the BAM is decoded (their insert
-     * parameters are set once the statistics are known) */
-    const int ws_fail = setup_workers(S);
-    int imean;
-    if (given) {
-        imean = g_mean;
-        lseq = g_lseq;
-        imin = g_min;
-        imax = g_max;
-        mapped = g_mapped;
-    } else {
-        imean = pd_insert_stats(pd, grom_prob2(S->num_sd), P->min_mapq, &lseq, &imin, &imax, &mapped);
+    R->t_started = clock_gettime_s();
+    return 0;
+}
+
+/* phase 2: the insert statistics, given or measured from the head of the BAM,
+ * with their printed lines (and, measured, <bam>.mean) */
+static int streamed_insert_stats(streamed_run *R) {
+    cli_state *S = R->S;
+    if (!R->given)
+        R->imean = pd_insert_stats(R->pd, grom_prob2(S->num_sd), S->P.min_mapq, &R->lseq, &R->imin, &R->imax, &R->mapped);
+    if (R->imean < 0) {
+        if (R->imean != -2) printf("ERROR: no reads to estimate the insert size from\n");
+        else if (S->env.verbose) printf("streamed decode stopped: %s\n", pd_error(R->pd));
+        return R->imean == -2 ? CLI_FALLBACK : 1;
     }
-    if (imean < 0) {
-        const int fallback = imean == -2;
-        if (!fallback) printf("ERROR: no reads to estimate the insert size from\n");
-        else if (S->verbose) printf("streamed decode stopped: %s\n", pd_error(pd));
-        pd_close(pd);
-        for (int i = 0; i < n_stages; i++) grom_stage_free(stages[i]);
-        free(dev_of);
-        return fallback ? CLI_FALLBACK : 1;
-    }
-    if (given) {
-        printf("Loading insert_mean et al from %s\n", mean_name);
-        t_insert_printed = 1;
-        grom_params_set_insert(&S->P, imean, imin, imax, lseq);
-        printf("insert mean, insert minimum, insert maximum: %d %d %d\n", S->P.insert_mean, imin, imax);
-        printf("median read length: %d\n", lseq);
-    } else {
-        print_insert(S, imean, lseq, imin, imax, mapped);
-    }
-    const double t_stats = clock_gettime_s();
-    int *keep = calloc(S->n_cand > 0 ? S->n_cand : 1, sizeof(int));
-    chrom_plan **plan = calloc(S->n_cand > 0 ? S->n_cand : 1, sizeof(chrom_plan *));
-    int *pidx = calloc(S->n_cand > 0 ? S->n_cand : 1, sizeof(int));
-    int n_plan = 0;
+    print_insert(S, R->given, R->imean, R->lseq, R->imin, R->imax, R->mapped);
+    R->t_stats = clock_gettime_s();
+    return 0;
+}
+
+/* phase 3: the final plan, told to the decoder, and the queue order: the
+ * device decoder's (longest first), else BAM order; rows are written in BAM
+ * order either way */
+static int streamed_plan(streamed_run *R) {
+    cli_state *S = R->S;
+    const int n1 = S->n_cand > 0 ? S->n_cand : 1;
+    R->keep = R->dev_of + n1;
+    R->pidx = R->keep + n1;
     for (int c = 0; c < S->n_cand; c++)
-        if ((keep[c] = passes_length(S, &S->plan[c])) && chrom_wanted(S->plan[c].name)) {
-            pidx[n_plan] = c;
-            plan[n_plan++] = &S->plan[c];
+        if ((R->keep[c] = passes_length(S, &S->plan[c])) && chrom_wanted(S, S->plan[c].name)) {
+            R->pidx[R->n_plan] = c;
+            R->plan[R->n_plan++] = &S->plan[c];
         }
-    pd_set_walk(pd, P->one_base_rd_len / 4 + 1, P->overlap_mult, P->insert_max_size, keep);
-    FILE *vcf = NULL;
-    grom_pool pool;
-    grom_worker *workers = NULL;
-    pthread_t *tids = NULL;
-    textbuf ctx_all = {0};
-    int next_write = 0, started = 0, fallback = 0;
-    int *qord = NULL, *qpos = NULL;
-    chrom_plan **qplan = NULL;
-    fasta_feed F;
-    memset(&F, 0, sizeof(F));
-    pthread_t fthr[FASTA_THREADS_MAX];
-    int fasta_started = 0, n_fthr = 0;
-    double t_ctx = 0.0;
-    if (ws_fail) { status = 1; goto done; }
+    pd_set_walk(R->pd, S->P.one_base_rd_len / 4 + 1, S->P.overlap_mult, S->P.insert_max_size, R->keep);
+    R->qord = R->pidx + n1;
+    R->qpos = R->qord + n1;
+    R->qplan = R->plan + n1;
+    for (int k = 0; k < R->n_plan; k++) R->qord[k] = k;
+    if (pd_device_mode(R->pd)) longest_first(R->qord, R->n_plan, R->plan);
+    for (int q = 0; q < R->n_plan; q++) {
+        R->qpos[R->qord[q]] = q;
+        R->qplan[q] = R->plan[R->qord[q]];
+    }
+    /* the scan contexts get the run's insert parameters; the rows' file is opened */
+    if (R->status) return 1; /* (the contexts could not be made) */
     for (int d = 0; d < S->n_init; d++)
-        if (grom_ctx_set_params(d, &S->P) != GROM_OK) { status = 1; goto done; }
-    t_ctx = clock_gettime_s();
-    vcf = fopen(S->out_name, "w");
-    if (!vcf) { printf("Error opening file %s\n", S->out_name); status = 1; goto done; }
-    if (S->one_chrom < 0) { /* (-c: rows only, the parent wrote the header) */
-        if (P->vcf == 1) header(vcf, S->fasta_name, 0);
-        else tab_header(vcf, P);
-    }
-    /* the order chromosomes are taken in: the device decoder's (longest
-     * first), else BAM order; rows are written in BAM order either way */
-    qord = malloc(sizeof(int) * (n_plan > 0 ? n_plan : 1));
-    qpos = malloc(sizeof(int) * (n_plan > 0 ? n_plan : 1));
-    qplan = malloc(sizeof(chrom_plan *) * (n_plan > 0 ? n_plan : 1));
-    for (int k = 0; k < n_plan; k++) qord[k] = k;
-    if (pd_device_mode(pd))
-        for (int a = 1; a < n_plan; a++)
-            for (int b = a; b > 0 && plan[qord[b]]->len > plan[qord[b - 1]]->len; b--) {
-                const int t = qord[b];
-                qord[b] = qord[b - 1];
-                qord[b - 1] = t;
-            }
-    for (int q = 0; q < n_plan; q++) {
-        qpos[qord[q]] = q;
-        qplan[q] = plan[qord[q]];
-    }
-    F.S = S;
-    F.plan = qplan;
-    F.n_plan = g_plan_only ? 0 : n_plan;
-    F.ahead = 4;
-    F.done = calloc((size_t)(n_plan > 0 ? n_plan : 1), 1);
-    pthread_mutex_init(&F.mu, NULL);
-    pthread_cond_init(&F.cv, NULL);
-    /* GROM_FASTA_THREADS (default 3) */
-    n_fthr = getenv("GROM_FASTA_THREADS") ? atoi(getenv("GROM_FASTA_THREADS")) : 3;
-    if (g_fdev) n_fthr = 1; /* the device loader: one thread feeds it */
-    if (n_fthr < 1) n_fthr = 1;
-    if (n_fthr > FASTA_THREADS_MAX) n_fthr = FASTA_THREADS_MAX;
-    for (int t = 0; t < n_fthr; t++)
-        if (pthread_create(&fthr[t], NULL, fasta_main, &F) != 0) {
-            n_fthr = t;
-            break;
-        }
-    if (n_fthr == 0) {
-        fprintf(stderr, "grom: no FASTA loader thread\n");
-        status = 1;
-        goto done;
-    }
-    fasta_started = 1;
-    /* (plan-only: the workers print each chromosome's plan line, so the host
-     * tests run the pool beside the streamed decoder) */
-    pool_start(&pool, S, n_plan, &workers, &tids);
-    pool.pos = qpos;
-    started = 1;
-    for (int q = 0; q < n_plan; q++) {
-        const int k = qord[q];
+        if (grom_ctx_set_params(d, &S->P) != GROM_OK) return 1;
+    R->t_ctx = clock_gettime_s();
+    R->pool.vcf = open_rows(S);
+    return R->pool.vcf == NULL;
+}
+
+/* phase 4: the FASTA loaders (GROM_FASTA_THREADS, default 3; the device
+ * loader is fed by one), working ahead of the hand-over in queue order */
+static int streamed_feed_start(streamed_run *R) {
+    cli_state *S = R->S;
+    fasta_feed *F = &R->F;
+    F->S = S;
+    F->plan = R->qplan;
+    F->n_plan = S->env.plan_only ? 0 : R->n_plan;
+    F->ahead = 4;
+    F->done = calloc((size_t)(R->n_plan > 0 ? R->n_plan : 1), 1);
+    pthread_mutex_init(&F->mu, NULL);
+    pthread_cond_init(&F->cv, NULL);
+    const int want = S->fdev ? 1 : S->env.fasta_threads;
+    while (F->n_thr < want && pthread_create(&F->thr[F->n_thr], NULL, fasta_main, F) == 0) F->n_thr++;
+    if (F->n_thr == 0) fprintf(stderr, "grom: no FASTA loader thread\n");
+    return F->n_thr == 0;
+}
+
+/* (references loaded but never handed to a worker are freed with the plan at
+ * the end of cli_run, after the workers are joined; a worker frees its own
+ * job's reference when its scan ends) */
+static void streamed_feed_stop(fasta_feed *F) {
+    if (!F->done) return;
+    pthread_mutex_lock(&F->mu);
+    F->stop = 1;
+    pthread_cond_broadcast(&F->cv);
+    pthread_mutex_unlock(&F->mu);
+    for (int t = 0; t < F->n_thr; t++) pthread_join(F->thr[t], NULL);
+    pthread_mutex_destroy(&F->mu);
+    pthread_cond_destroy(&F->cv);
+    free(F->done);
+}
+
+/* phase 5: every chromosome of the queue, once the decoder has staged it and
+ * its reference is loaded, goes to the scan workers; rows that are ready are
+ * written meanwhile.  (Plan-only: the workers print each chromosome's plan
+ * line, so the host tests run the pool beside the streamed decoder) */
+static void streamed_hand_over(streamed_run *R) {
+    cli_state *S = R->S;
+    fasta_feed *F = &R->F;
+    grom_pool *pool = &R->pool;
+    pool_start(pool, S, R->n_plan);
+    pool->pos = R->qpos;
+    for (int q = 0; q < R->n_plan; q++) {
+        chrom_plan *c = R->qplan[q];
+        const int cand = R->pidx[R->qord[q]];
         grom_stage *st = NULL;
         pd_chrom_facts facts;
-        const int rc = pd_wait_chrom(pd, pidx[k], &st, &facts);
-        if (rc == 1) { fallback = 1; break; }
+        const int rc = pd_wait_chrom(R->pd, cand, &st, &facts);
+        if (rc == 1) { R->fallback = 1; break; }
         if (rc != 0) {
-            fprintf(stderr, "grom: streamed decode failed: %s\n", pd_error(pd));
-            grom_set_last_error(pd_error(pd));
-            status = 1;
+            fprintf(stderr, "grom: streamed decode failed: %s\n", pd_error(R->pd));
+            grom_set_last_error(pd_error(R->pd));
+            R->status = 1;
             break;
         }
-        if (!g_plan_only) {
-            pthread_mutex_lock(&F.mu);
-            while (F.loaded <= q) pthread_cond_wait(&F.cv, &F.mu);
-            F.consumed = q + 1;
-            pthread_cond_broadcast(&F.cv);
-            pthread_mutex_unlock(&F.mu);
+        if (!S->env.plan_only) {
+            pthread_mutex_lock(&F->mu);
+            while (F->loaded <= q) pthread_cond_wait(&F->cv, &F->mu);
+            F->consumed = q + 1;
+            pthread_cond_broadcast(&F->cv);
+            pthread_mutex_unlock(&F->mu);
             /* the device loader's bytes go stage-ward device-to-device (same GPU), else from the host copy */
-            const int d2d = plan[k]->ref && plan[k]->d_ref && dev_of[pidx[k]] == g_fdev_device;
-            if (!plan[k]->ref || (d2d ? grom_stage_set_ref_device(st, plan[k]->d_ref, plan[k]->len)
-                                      : grom_stage_set_ref(st, plan[k]->ref, plan[k]->len)) != GROM_OK) {
-                fprintf(stderr, "grom: staging the reference of %s failed: %s\n", plan[k]->name, grom_last_error());
-                status = 1;
-                pd_release_stage(pd, st);
+            const int d2d = c->ref && c->d_ref && R->dev_of[cand] == S->device;
+            if (!c->ref || (d2d ? grom_stage_set_ref_device(st, c->d_ref, c->len)
+                                : grom_stage_set_ref(st, c->ref, c->len)) != GROM_OK) {
+                fprintf(stderr, "grom: staging the reference of %s failed: %s\n", c->name, grom_last_error());
+                R->status = 1;
+                pd_release_stage(R->pd, st);
                 break;
             }
         }
-        pthread_mutex_lock(&pool.mu);
-        grom_job *j = &pool.jobs[q];
-        j->cp = plan[k];
+        pthread_mutex_lock(&pool->mu);
+        grom_job *j = &pool->jobs[q];
+        j->cp = c;
         j->stage = st;
         j->facts = facts;
-        j->pd = pd;
-        j->k = pidx[k];
-        j->device = dev_of[pidx[k]];
-        pd_trace(pd, PD_EV_HANDED, pidx[k], 0);
+        j->pd = R->pd;
+        j->k = cand;
+        j->device = R->dev_of[cand];
+        pd_trace(R->pd, PD_EV_HANDED, cand, 0);
         j->ready = 1;
-        pthread_cond_broadcast(&pool.cv);
-        drain_rows(&pool, &next_write, n_plan, vcf, &ctx_all, &status);
-        pthread_mutex_unlock(&pool.mu);
+        pthread_cond_broadcast(&pool->cv);
+        drain_rows(pool, R->n_plan);
+        pthread_mutex_unlock(&pool->mu);
     }
-done:
-    if (fasta_started) {
-        pthread_mutex_lock(&F.mu);
-        F.stop = 1;
-        pthread_cond_broadcast(&F.cv);
-        pthread_mutex_unlock(&F.mu);
-        for (int t = 0; t < n_fthr; t++) pthread_join(fthr[t], NULL);
-        /* references loaded but never handed to a worker are freed with the
-         * plan at the end of cli_run, after the workers are joined (a worker
-         * frees its own job's reference when its scan ends) */
-        pthread_mutex_destroy(&F.mu);
-        pthread_cond_destroy(&F.cv);
-    }
-    free(F.done);
-    const double t_loop = clock_gettime_s();
-    if (started) pool_finish(&pool, S, workers, tids, &next_write, vcf, &ctx_all, &status);
-    if (!fallback && status == 0 && S->verbose) {
-        const double t_end = clock_gettime_s();
-        printf("cli phases (s from start): candidates/FASTA lengths %.3f, decoder open %.3f, insert statistics %.3f, "
-               "contexts %.3f, last chromosome handed %.3f, scans done %.3f; process start to CLI start %.3f\n",
-               S->t_cand - S->t_cli0, t_started - S->t_cli0, t_stats - S->t_cli0, t_ctx - S->t_cli0, t_loop - S->t_cli0,
-               t_end - S->t_cli0, S->t_load);
-        pd_counters pc;
-        pd_get_counters(pd, &pc);
-        if (pc.device)
-            printf("device decode: %lld records, %.2f GB compressed read and copied to HBM, %.2f GB inflated on the GPU; "
-                   "file reads %.2f s (read ahead; waited for %.2f s), device work %.2f s (GPU inflate %.3f s, record walk %.3f s, "
-                   "parse %.3f s; %lld of %lld walk sub-chunks re-walked), device buffer growth %.3f s, per-chromosome decode + "
-                   "finalise %.2f s, idle stage blocks reclaimed %lld, %d decode workers, %lld statistics-only runs, wall %.2f s\n",
-                   (long long)pc.records, pc.compressed_bytes / 1e9, pc.inflated_bytes / 1e9, pc.io_s, pc.wait_s,
-                   pc.decode_thread_s,
-                   pc.gpu_ms[0] / 1e3, pc.gpu_ms[1] / 1e3, pc.gpu_ms[2] / 1e3, (long long)pc.rewalked, (long long)pc.subchunks,
-                   pc.gpu_ms[3] / 1e3, pc.upload_s, (long long)pc.reclaimed, pc.dd_workers, (long long)pc.stats_only_runs,
-                   clock_gettime_s() - t_start);
-        else
+}
+
+/* phase 6 (GROM_VERBOSE): the phases' times and the decoder's counters; bench.py reads these lines */
+static void streamed_report(const streamed_run *R) {
+    const cli_state *S = R->S;
+    const double t_end = clock_gettime_s();
+    printf("cli phases (s from start): candidates/FASTA lengths %.3f, decoder open %.3f, insert statistics %.3f, "
+           "contexts %.3f, last chromosome handed %.3f, scans done %.3f; process start to CLI start %.3f\n",
+           S->t_cand - S->t_cli0, R->t_started - S->t_cli0, R->t_stats - S->t_cli0, R->t_ctx - S->t_cli0,
+           R->t_loop - S->t_cli0, t_end - S->t_cli0, S->t_load);
+    pd_counters pc;
+    pd_get_counters(R->pd, &pc);
+    if (pc.device)
+        printf("device decode: %lld records, %.2f GB compressed read and copied to HBM, %.2f GB inflated on the GPU; "
+               "file reads %.2f s (read ahead; waited for %.2f s), device work %.2f s (GPU inflate %.3f s, record walk %.3f s, "
+               "parse %.3f s; %lld of %lld walk sub-chunks re-walked), device buffer growth %.3f s, per-chromosome decode + "
+               "finalise %.2f s, idle stage blocks reclaimed %lld, %d decode workers, %lld statistics-only runs, wall %.2f s\n",
+               (long long)pc.records, pc.compressed_bytes / 1e9, pc.inflated_bytes / 1e9, pc.io_s, pc.wait_s,
+               pc.decode_thread_s,
+               pc.gpu_ms[0] / 1e3, pc.gpu_ms[1] / 1e3, pc.gpu_ms[2] / 1e3, (long long)pc.rewalked, (long long)pc.subchunks,
+               pc.gpu_ms[3] / 1e3, pc.upload_s, (long long)pc.reclaimed, pc.dd_workers, (long long)pc.stats_only_runs,
+               clock_gettime_s() - R->t_start);
+    else
         printf("streamed decode: %lld records in %lld pieces, %d threads (%s), %.2f GB inflated, %.2f GB to HBM, "
                "decoder busy %.2f s (inflate %.2f s, file reads %.2f s), uploader %.2f s (waiting %.2f s), wall %.2f s\n",
                (long long)pc.records, (long long)pc.pieces, pc.threads, pc.libdeflate ? "libdeflate" : "zlib",
                pc.inflated_bytes / 1e9, pc.h2d_bytes / 1e9, pc.decode_thread_s, pc.inflate_s, pc.io_s, pc.upload_s, pc.wait_s,
-               clock_gettime_s() - t_start);
-    }
+               clock_gettime_s() - R->t_start);
+}
+
+/* phase 7: the outputs, before any device memory is freed (that is teardown).
+ * GROM_CLI_PROCESS=1 (opt-in, for a `grom` process; never for in-process
+ * callers such as the Python binding): the process ends here */
+static void streamed_outputs(streamed_run *R) {
+    cli_state *S = R->S;
+    const int good = !R->fallback && R->status == 0;
     S->t_scans = clock_gettime_s();
-    /* the outputs first: freeing the stages and contexts is teardown */
-    if (vcf) fclose(vcf);
-    if (!fallback && status == 0) finish_outputs(S, &ctx_all);
+    if (R->pool.vcf) fclose(R->pool.vcf);
+    if (good) finish_outputs(S, &R->pool.ctx_all);
     S->t_outputs = clock_gettime_s();
-    if (!fallback && status == 0 && cli_process_exit()) {
-        /* the `grom` executable ends here: every scan has finished and the
-         * outputs are closed; the process's device memory, streams and pinned
-         * buffers go with it (hipFree of ~150 GB of stages and scratch, and
-         * the runtime's own teardown, are 0.1-0.6 s of a whole run) */
-        if (S->verbose)
-            printf("cli teardown (s from start): scans done %.3f, outputs %.3f, process exit without freeing\n",
-                   S->t_scans - S->t_cli0, S->t_outputs - S->t_cli0);
-        fflush(stdout);
-        fflush(stderr);
-        /* GROM_EXIT_HANDLERS=1: exit handlers still run (a profiler that
-         * writes its records at exit, e.g. rocprofv3) */
-        const char *eh = getenv("GROM_EXIT_HANDLERS");
-        if (eh && atoi(eh) == 1) exit(0);
-        _exit(0);
-    }
-    pd_close(pd);
+    if (!good || !S->env.cli_process) return;
+    /* every scan has finished and the outputs are closed; the process's
+     * device memory, streams and pinned buffers go with it (hipFree of
+     * ~150 GB of stages and scratch, and the runtime's own teardown, are
+     * 0.1-0.6 s of a whole run) */
+    if (S->env.verbose)
+        printf("cli teardown (s from start): scans done %.3f, outputs %.3f, process exit without freeing\n",
+               S->t_scans - S->t_cli0, S->t_outputs - S->t_cli0);
+    fflush(stdout);
+    fflush(stderr);
+    /* GROM_EXIT_HANDLERS=1: exit handlers still run (a profiler that
+     * writes its records at exit, e.g. rocprofv3) */
+    if (S->env.exit_handlers) exit(0);
+    _exit(0);
+}
+
+/* phase 8, and every way out: the decoder closed, the stages freed, the
+ * arrays released.  `rc`: an early phase's verdict, else the run's */
+static int streamed_close(streamed_run *R, int rc) {
+    cli_state *S = R->S;
+    if (R->pd) pd_close(R->pd);
     S->t_decclose = clock_gettime_s();
-    if (getenv("GROM_PAR_FREE") && atoi(getenv("GROM_PAR_FREE")) == 1 && n_stages > 1) {
+    if (S->env.par_free && R->n_stages > 1) {
         /* (timing probe) the stages freed on threads of their own */
         pthread_t th[64];
         int started[64] = {0};
-        for (int i = 0; i < n_stages && i < 64; i++)
-            started[i] = pthread_create(&th[i], NULL, stage_free_main, stages[i]) == 0;
-        for (int i = 0; i < n_stages; i++) {
+        for (int i = 0; i < R->n_stages && i < 64; i++)
+            started[i] = pthread_create(&th[i], NULL, stage_free_main, R->stages[i]) == 0;
+        for (int i = 0; i < R->n_stages; i++) {
             if (i < 64 && started[i]) pthread_join(th[i], NULL);
-            else grom_stage_free(stages[i]);
+            else grom_stage_free(R->stages[i]);
         }
     } else {
-        for (int i = 0; i < n_stages; i++) grom_stage_free(stages[i]);
+        for (int i = 0; i < R->n_stages; i++) grom_stage_free(R->stages[i]);
     }
     S->t_pdclose = clock_gettime_s();
-    free(ctx_all.p);
-    free(plan);
-    free(pidx);
-    free(keep);
-    free(dev_of);
-    free(qord);
-    free(qpos);
-    free(qplan);
-    if (fallback) {
+    free(R->pool.ctx_all.p);
+    free(R->plan);
+    free(R->dev_of);
+    if (rc) return rc;
+    if (R->fallback) {
         for (int d = 0; d < S->n_init; d++) grom_dev_fini(d);
         S->n_init = 0;
         return CLI_FALLBACK;
     }
-    return status;
+    return R->status;
 }
 
-/* GROM_SEGV_TRACE=1 (diagnostics for in-process callers such as the Python
- * binding, which have no handler of the grom executable's): a fatal signal
- * prints the host stack before the process ends */
+static int run_streamed(cli_state *S) {
+    streamed_run run = {.S = S, .t_start = clock_gettime_s()}, *R = &run;
+    int rc = streamed_open(R);
+    /* the scan contexts while the head of the BAM is decoded (their insert
+     * parameters are set once the statistics are known) */
+    if (!rc) R->status = setup_workers(S) != 0;
+    if (!rc) rc = streamed_insert_stats(R);
+    if (!rc) { /* from here on a failure is the run's status, and its times are reported */
+        if (streamed_plan(R) || streamed_feed_start(R)) R->status = 1;
+        else streamed_hand_over(R);
+        streamed_feed_stop(&R->F);
+        R->t_loop = clock_gettime_s();
+        if (R->pool.jobs) pool_finish(&R->pool);
+        if (R->pool.status) R->status = 1;
+        if (!R->fallback && R->status == 0 && S->env.verbose) streamed_report(R);
+        streamed_outputs(R);
+    }
+    return streamed_close(R, rc);
+}
+
+/* A fatal signal prints the host stack before the process ends (addresses
+ * resolve with addr2line against libgrom_amd.so): the grom executable's
+ * handler (`abrt`: SIGABRT too), and with GROM_SEGV_TRACE=1 that of in-process
+ * callers such as the Python binding, which have none */
 static void on_fatal_trace(int sig) {
     void *fr[64];
     const int n = backtrace(fr, 64);
@@ -1778,6 +1623,13 @@ static void on_fatal_trace(int sig) {
     backtrace_symbols_fd(fr, n, 2);
     signal(sig, SIG_DFL);
     raise(sig);
+}
+
+void cli_trace_fatal_signals(int abrt) {
+    struct sigaction sa = {.sa_handler = on_fatal_trace};
+    sigaction(SIGBUS, &sa, NULL);
+    sigaction(SIGSEGV, &sa, NULL);
+    if (abrt) sigaction(SIGABRT, &sa, NULL);
 }
 
 /* 1 if a file stands where the BAM's index is looked for (<bam>.bai or
@@ -1794,30 +1646,19 @@ static int index_file_present(const char *bam_path) {
     return 0;
 }
 
-static int cli_run(int argc, char **argv, int force_serial) {
-    if (getenv("GROM_SEGV_TRACE")) {
-        struct sigaction sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.sa_handler = on_fatal_trace;
-        sigaction(SIGSEGV, &sa, NULL);
-        sigaction(SIGBUS, &sa, NULL);
-    }
-    optind = 0; /* GNU getopt: 0 fully re-initialises, so this is callable again */
-    setlinebuf(stdout);
-    cli_state *S = calloc(1, sizeof(cli_state));
-    S->t_cli0 = clock_gettime_s();
-    S->t_load = since_process_start();
+/* phase: the options into the state (getopt string of GROM.c:21908).
+ * -1: go on; else the exit code (-h, a bad option) */
+static int cli_parse(cli_state *S, int argc, char **argv) {
     grom_params *P = &S->P;
     grom_default_params(P);
     S->max_chr_len = 300000000; /* g_max_chr_fasta_len, GROM.c:946 */
     S->num_sd = 3;
-    S->verbose = getenv("GROM_VERBOSE") != NULL;
     S->n_dev = 1;
     S->one_chrom = -1;
     S->sub_end = 300000000; /* MAX_REGION, GROM.c:78 */
-    if (getenv("GROM_DEVICE")) S->device = atoi(getenv("GROM_DEVICE"));
-    int opt, ret = 1;
-    /* getopt string of GROM.c:21908 */
+    S->device = S->env.device;
+    optind = 0; /* GNU getopt: 0 fully re-initialises, so this is callable again */
+    int opt;
     while ((opt = getopt(argc, argv,
                          "Z:W:X:Q:A:Y:B:D:E:K:N:V:U:L:F:SP:c:R:MG:i:r:o:p:q:s:v:g:l:d:b:n:a:y:z:e:fj:k:m:u:w:x:h")) != -1) {
         switch (opt) {
@@ -1826,7 +1667,7 @@ static int cli_run(int argc, char **argv, int force_serial) {
         case 'M': P->rmdup = 1; break;
         case 'i': S->bam_name = optarg; break;
         case 'r': S->fasta_name = optarg; break;
-        case 'o': S->out_name = optarg; g_side_base = optarg; break;
+        case 'o': S->out_name = S->side_base = optarg; break;
         case 'B': S->max_chr_len = atol(optarg); break;
         case 'p': P->ploidy = atoi(optarg); break;
         case 'q': P->min_mapq = atoi(optarg); break;
@@ -1844,8 +1685,7 @@ static int cli_run(int argc, char **argv, int force_serial) {
             break;
         case 'P': { /* -P processes -> GPUs; 0 or beyond 256: serial, one GPU (GROM.c:21923-21927) */
             const int n = atoi(optarg);
-            const char *ps = getenv("GROM_P_SERIAL");
-            S->fetch = n >= 1 && n <= 256 && !(ps && atoi(ps) == 1);
+            S->fetch = n >= 1 && n <= 256 && !S->env.p_serial;
             S->n_dev = n >= 1 && n <= 256 ? n : 1;
             break;
         }
@@ -1872,83 +1712,107 @@ static int cli_run(int argc, char **argv, int force_serial) {
         case 'u': P->max_evidence_ratio = atof(optarg); break;
         case 'w': P->max_ins_range = atoi(optarg); break;
         case 'N': P->gen1000_window = atol(optarg); break;
-        case 'h': print_help(); free(S); return 0;
-        case '?': free(S); return 1;
+        case 'h': print_help(); return 0;
+        case '?': return 1;
         default: break; /* accepted; steers rows outside the implemented scan */
         }
     }
     P->rd_min_mapq = P->min_mapq;         /* GROM.c:22102 */
     P->pval_threshold1 = P->pval_threshold; /* GROM.c:22101 */
     P->sv_list2_len = P->sv_list_len / 10;  /* GROM.c:21925 */
-    if (!force_serial) {
+    if (!S->force_serial) {
         printf("bam %s\n", S->bam_name ? S->bam_name : "(null)");
         printf("ref %s\n", S->fasta_name ? S->fasta_name : "(null)");
         printf("results %s\n", S->out_name ? S->out_name : "(null)");
     }
-    if (!S->bam_name) { printf("ERROR: No bam file specified.\n"); free(S); return 1; }
-    {
-        bgzf_reader br;
-        if (bgzf_open_read(&br, S->bam_name) != 0 || bam_read_header(&br, &S->hdr) != 0) {
-            printf("\nCould not open %s\n", S->bam_name);
-            bgzf_close_read(&br);
-            free(S);
-            return 1;
-        }
-        bgzf_close_read(&br);
-    }
-    /* GROM_BUILD_INDEX=1: a BAM with no index file gets one, built on the run's
-     * device (grom_bai_build_device); a file that is there is never replaced */
-    if (getenv("GROM_BUILD_INDEX") && atoi(getenv("GROM_BUILD_INDEX")) != 0 && !index_file_present(S->bam_name)) {
+    if (!S->bam_name) { printf("ERROR: No bam file specified.\n"); return 1; }
+    return -1;
+}
+
+/* phase: the BAM's header and index, and the output's name checked.
+ * GROM_BUILD_INDEX=1: a BAM with no index file gets one, built on the run's
+ * device (grom_bai_build_device); a file that is there is never replaced */
+static int cli_open_bam(cli_state *S) {
+    bgzf_reader br;
+    const int bad = bgzf_open_read(&br, S->bam_name) != 0 || bam_read_header(&br, &S->hdr) != 0;
+    bgzf_close_read(&br);
+    if (bad) { printf("\nCould not open %s\n", S->bam_name); return 1; }
+    if (S->env.build_index && !index_file_present(S->bam_name)) {
         int64_t bo[8];
         if (grom_bai_build_device(S->bam_name, NULL, S->device, bo) != 0) {
             printf("Could not build the BAM index: %s\n", grom_last_error());
-            goto out_hdr;
+            return 1;
         }
         printf("built %s.bai on device %d in %.3f s (%lld records, %.3f s on the device)\n", S->bam_name, S->device,
                (double)bo[7] / 1e6, (long long)bo[0], (double)bo[6] / 1e6);
     }
-    if (!bai_loads(S->bam_name)) { printf("Could not open BAM indexing file\n"); goto out_hdr; }
-    if (!S->out_name) { printf("ERROR: No output file specified.\n"); goto out_hdr; }
+    if (!bai_loads(S->bam_name)) { printf("Could not open BAM indexing file\n"); return 1; }
+    if (!S->out_name) { printf("ERROR: No output file specified.\n"); return 1; }
     if (S->one_chrom >= 0) {
-        if (S->one_chrom >= S->hdr.n_ref) { printf("ERROR: -c %d: the BAM has %d targets\n", S->one_chrom, S->hdr.n_ref); goto out_hdr; }
+        if (S->one_chrom >= S->hdr.n_ref) { printf("ERROR: -c %d: the BAM has %d targets\n", S->one_chrom, S->hdr.n_ref); return 1; }
         if (S->sub_start != 0) {
             printf("ERROR: -c with a sub-region (start %d): only whole-chromosome children are supported (-R is not)\n",
                    S->sub_start);
-            goto out_hdr;
+            return 1;
         }
         S->fetch = 1; /* g_parallel_mode = 1, GROM.c:22104 */
         snprintf(S->part_name, sizeof(S->part_name), "%s.%s-%d", S->out_name, S->hdr.ref_name[S->one_chrom], S->sub_child);
         S->out_name = S->part_name;
     } else {
         FILE *probe = fopen(S->out_name, "w");
-        if (!probe) { printf("\nCould not open %s\n", S->out_name); goto out_hdr; }
+        if (!probe) { printf("\nCould not open %s\n", S->out_name); return 1; }
         fclose(probe);
     }
-    if (!S->fasta_name) { printf("ERROR: No reference file specified.\n"); goto out_hdr; }
-    g_plan_only = getenv("GROM_PLAN_ONLY") != NULL;
-    if (cli_fasta_open(S, force_serial) != 0) goto out_hdr;
-    if (!g_plan_only && !S->hip_started && !S->hip_done)
-        S->hip_started = pthread_create(&S->hip_thr, NULL, hip_init_main, &S->device) == 0;
-    fp_sampler fps;
-    memset(&fps, 0, sizeof(fps));
-    if (!g_plan_only && S->verbose) fp_start(&fps, S->device);
-    /* tables (read_binom_tables, GROM.c:22234) on a thread beside the decode */
-    {
-        size_t tn = (size_t)(GROM_MAX_TRIALS + 1) * (GROM_MAX_TRIALS + 1);
-        S->hez = malloc(sizeof(double) * tn);
-        S->mq = malloc(sizeof(double) * tn);
-        S->tables_started = pthread_create(&S->tables_thr, NULL, tables_main, S) == 0;
-        if (!S->tables_started) grom_build_tables(P->min_mapq, S->hez, S->mq);
+    return 0;
+}
+
+/* phase: -r opened; then, beside what follows, the HIP start-up, the
+ * footprint sampler (GROM_VERBOSE) and the tables (read_binom_tables,
+ * GROM.c:22234) on threads of their own */
+static int cli_open_fasta(cli_state *S, fp_sampler *fps) {
+    if (!S->fasta_name) { printf("ERROR: No reference file specified.\n"); return 1; }
+    if (cli_fasta_open(S) != 0) {
+        memset(&S->fa, 0, sizeof(S->fa)); /* (what a failed open leaves is not for grom_fasta_close) */
+        return 1;
     }
-    /* candidate chromosomes in BAM header order (GROM.c:20826-21050); the
-     * length test that needs the insert size comes later */
-    S->plan = calloc(S->hdr.n_ref > 0 ? S->hdr.n_ref : 1, sizeof(chrom_plan));
-    /* the loader's length of every matched FASTA entry (find_disc_svs loads
-     * each chromosome, GROM.c:21009-21045), several entries at once */
-    int *fi_of = malloc(sizeof(int) * (S->hdr.n_ref > 0 ? S->hdr.n_ref : 1));
-    int *fi_list = malloc(sizeof(int) * (S->hdr.n_ref > 0 ? S->hdr.n_ref : 1));
+    if (!S->env.plan_only && !S->hip_started && !S->hip_done) hip_start(S);
+    if (!S->env.plan_only && S->env.verbose) fp_start(fps, S->device);
+    const size_t tn = (size_t)(GROM_MAX_TRIALS + 1) * (GROM_MAX_TRIALS + 1);
+    S->hez = malloc(sizeof(double) * tn);
+    S->mq = malloc(sizeof(double) * tn);
+    S->tables_started = pthread_create(&S->tables_thr, NULL, tables_main, S) == 0;
+    if (!S->tables_started) grom_build_tables(S->P.min_mapq, S->hez, S->mq);
+    return 0;
+}
+
+/* the loader's length of every matched FASTA entry (find_disc_svs loads each
+ * chromosome, GROM.c:21009-21045), several entries at once: fi_len[entry] */
+static void fasta_lengths(cli_state *S, const int *fi_list, int n_fi, long *fi_len) {
+    if (S->fdev) {
+        /* the index pass measured them; a table adopted from .info: a length-only load each */
+        for (int a = 0; a < n_fi; a++) {
+            int64_t L = grom_fasta_dev_load(S->fdev, fi_list[a], NULL, 0, NULL);
+            if (L < 0) L = cli_fasta_host_load(S, fi_list[a], NULL, 0);
+            fi_len[fi_list[a]] = (long)L;
+        }
+        return;
+    }
+    long *lens = calloc(n_fi > 0 ? n_fi : 1, sizeof(long));
+    const int thr = host_cpus() < 16 ? host_cpus() : 16;
+    const int ok = !S->env.fasta_serial && grom_fasta_lengths(&S->fa, fi_list, n_fi, lens, thr) == 0;
+    for (int a = 0; a < n_fi; a++) fi_len[fi_list[a]] = ok ? lens[a] : grom_fasta_load(&S->fa, fi_list[a], NULL, 0);
+    free(lens);
+}
+
+/* phase: the candidate chromosomes in BAM header order (GROM.c:20826-21050);
+ * the length test that needs the insert size comes later */
+static int cli_candidates(cli_state *S) {
+    const int n1 = S->hdr.n_ref > 0 ? S->hdr.n_ref : 1;
+    S->plan = calloc(n1, sizeof(chrom_plan));
+    int *fi_of = malloc(sizeof(int) * n1);   /* target -> FASTA entry, -1: none */
+    int *fi_list = malloc(sizeof(int) * n1); /* the distinct entries */
     long *fi_len = calloc(S->fa.n > 0 ? S->fa.n : 1, sizeof(long));
-    int n_fi = 0;
+    int n_fi = 0, rc = 0;
     for (int t = 0; t < S->hdr.n_ref; t++) {
         if (S->one_chrom >= 0 && t != S->one_chrom) { /* -c: loop_start = g_one_chromosome, GROM.c:20821 */
             fi_of[t] = -1;
@@ -1957,38 +1821,23 @@ static int cli_run(int argc, char **argv, int force_serial) {
         int fi = grom_match_target(&S->fa, S->hdr.ref_name[t]);
         char lc[GROM_MAX_CHR_NAMES];
         int bl = grom_target_name_lc(S->hdr.ref_name[t], lc, (int)sizeof(lc));
-        if (P->gender == 0 && ((bl == 4 && strncmp(lc, "chry", 4) == 0) || (bl == 1 && lc[0] == 'y'))) fi = -1;
+        if (S->P.gender == 0 && ((bl == 4 && strncmp(lc, "chry", 4) == 0) || (bl == 1 && lc[0] == 'y'))) fi = -1;
         fi_of[t] = fi;
         if (fi < 0) continue;
         int seen = 0;
         for (int a = 0; a < n_fi && !seen; a++) seen = fi_list[a] == fi;
         if (!seen) fi_list[n_fi++] = fi;
     }
-    {
-        long *lens = calloc(n_fi > 0 ? n_fi : 1, sizeof(long));
-        const int thr = host_cpus() < 16 ? host_cpus() : 16;
-        if (g_fdev) {
-            /* the index pass measured them; a table adopted from .info: a length-only load each */
-            for (int a = 0; a < n_fi; a++) {
-                int64_t L = grom_fasta_dev_load(g_fdev, fi_list[a], NULL, 0, NULL);
-                if (L < 0) L = cli_fasta_host_load(S, fi_list[a], NULL, 0);
-                fi_len[fi_list[a]] = (long)L;
-            }
-        } else {
-        const int ok = getenv("GROM_FASTA_SERIAL") == NULL && grom_fasta_lengths(&S->fa, fi_list, n_fi, lens, thr) == 0;
-        for (int a = 0; a < n_fi; a++) fi_len[fi_list[a]] = ok ? lens[a] : grom_fasta_load(&S->fa, fi_list[a], NULL, 0);
-        }
-        free(lens);
-    }
-    for (int t = 0; t < S->hdr.n_ref; t++) {
+    fasta_lengths(S, fi_list, n_fi, fi_len);
+    for (int t = 0; t < S->hdr.n_ref && rc == 0; t++) {
         const int fi = fi_of[t];
         if (fi < 0) continue;
         long len = fi_len[fi];
         if (S->one_chrom >= 0 && len > S->sub_end) {
             printf("ERROR: -c region end %d is inside the chromosome (%ld bases): -R sub-regions are not supported\n",
                    S->sub_end, len);
-            free(fi_of); free(fi_list); free(fi_len);
-            goto out_hdr;
+            rc = 1;
+            continue;
         }
         /* count_discordant_pairs re-derives the BAM target from the FASTA name
          * (GROM.c:1894-1961): the first target matching it */
@@ -2007,73 +1856,95 @@ static int cli_run(int argc, char **argv, int force_serial) {
     free(fi_list);
     free(fi_len);
     S->t_cand = clock_gettime_s();
-    {
-        size_t ol = strlen(S->out_name);
-        if (S->one_chrom >= 0) /* the child's partial CTX file, GROM.c:20686 */
-            snprintf(S->ctx_name, sizeof(S->ctx_name), "%s.ctx", S->out_name);
-        else if (ol > 4 && strcmp(S->out_name + ol - 4, ".vcf") == 0)
-            snprintf(S->ctx_name, sizeof(S->ctx_name), "%.*s.ctx.vcf", (int)(ol - 4), S->out_name);
-        else
-            snprintf(S->ctx_name, sizeof(S->ctx_name), "%s.ctx", S->out_name);
-    }
-    const char *ser = getenv("GROM_SERIAL_DECODE");
-    if (force_serial || (ser && atoi(ser) > 0)) ret = run_serial(S);
-    else ret = run_streamed(S);
-    if (g_fdev && S->verbose) {
+    return rc;
+}
+
+/* phase: the CTX file's name, after the rows' (-c: the child's partial CTX file, GROM.c:20686) */
+static void cli_name_outputs(cli_state *S) {
+    const size_t ol = strlen(S->out_name);
+    if (S->one_chrom < 0 && ol > 4 && strcmp(S->out_name + ol - 4, ".vcf") == 0)
+        snprintf(S->ctx_name, sizeof(S->ctx_name), "%.*s.ctx.vcf", (int)(ol - 4), S->out_name);
+    else
+        snprintf(S->ctx_name, sizeof(S->ctx_name), "%s.ctx", S->out_name);
+}
+
+/* phase (GROM_VERBOSE): the device FASTA loader's times, the teardown's, the footprint */
+static void cli_report(cli_state *S, fp_sampler *fps) {
+    if (S->fdev && S->env.verbose) {
         double ms[8];
-        grom_fasta_dev_times(g_fdev, ms);
+        grom_fasta_dev_times(S->fdev, ms);
         fprintf(stderr, "grom: device FASTA loader (%s, device %d): file read + upload %.1f ms, inflate %.1f ms, index pass "
                         "kernels %.1f ms, load kernels %.1f ms, copies to the host %.1f ms; wall: open %.1f ms, index %.1f ms, "
-                        "loads %.1f ms\n", grom_fasta_dev_is_bgzf(g_fdev) ? "BGZF" : grom_fasta_dev_kind(g_fdev) == 2 ? "gzip" : "plain text",
-                g_fdev_device, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6], ms[7]);
-        if (grom_fasta_dev_kind(g_fdev) == 2) {
+                        "loads %.1f ms\n", grom_fasta_dev_is_bgzf(S->fdev) ? "BGZF" : grom_fasta_dev_kind(S->fdev) == 2 ? "gzip" : "plain text",
+                S->device, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6], ms[7]);
+        if (grom_fasta_dev_kind(S->fdev) == 2) {
             int64_t gs[8];
             double gm[6];
-            grom_fasta_dev_gzip_stats(g_fdev, gs, gm);
+            grom_fasta_dev_gzip_stats(S->fdev, gs, gm);
             fprintf(stderr, "grom: gzip on the device: %lld units (%lld from guesses, %lld decoded again) in %lld members, "
                             "%lld marker bytes, scratch %.1f MB; guess %.1f ms, count %.1f ms, symbols %.1f ms, hand-over "
                             "%.1f ms, resolve %.1f ms, CRC %.1f ms\n", (long long)gs[0], (long long)gs[1], (long long)gs[2],
                     (long long)gs[4], (long long)gs[3], gs[6] / 1048576.0, gm[0], gm[1], gm[2], gm[3], gm[4], gm[5]);
         }
     }
-    tables_join(S);
     for (int d = 0; d < S->n_init; d++) grom_dev_fini(d);
-    if (S->verbose && S->t_outputs > 0)
+    if (S->env.verbose && S->t_outputs > 0)
         printf("cli teardown (s from start): scans done %.3f, outputs %.3f, decoder closed %.3f, stages freed %.3f, "
                "contexts freed %.3f\n", S->t_scans - S->t_cli0, S->t_outputs - S->t_cli0, S->t_decclose - S->t_cli0,
                S->t_pdclose - S->t_cli0, clock_gettime_s() - S->t_cli0);
-    if (fps.started) fp_stop(&fps, clock_gettime_s() - S->t_cli0);
+    fp_stop(fps, clock_gettime_s() - S->t_cli0);
+}
+
+/* phase: whatever the run made is released */
+static void cli_release(cli_state *S, fp_sampler *fps) {
+    tables_join(S);
+    hip_ready(S);
+    fp_stop(fps, -1.0); /* (a run that ended before its report: no line) */
     for (int i = 0; i < S->n_cand; i++) {
         free(S->plan[i].target);
         free(S->plan[i].ref);
-        plan_release_dref(&S->plan[i]);
+        plan_release_dref(S, &S->plan[i]);
     }
     free(S->plan);
     free(S->hez);
     free(S->mq);
+    free(S->vcf_segs.p);
     grom_fasta_close(&S->fa);
-out_hdr:
-    tables_join(S);
-    hip_ready(S);
-    if (g_fdev) {
-        pthread_mutex_lock(&g_fdev_mu);
-        grom_fasta_dev_close(g_fdev);
-        g_fdev = NULL;
-        g_fdev_device = -1;
-        pthread_mutex_unlock(&g_fdev_mu);
-    }
+    grom_fasta_dev_close(S->fdev);
     dd_ctx_drop_prepared();
     bam_free_header(&S->hdr);
+}
+
+static int cli_run(int argc, char **argv, int force_serial, int *insert_printed) {
+    cli_state *S = calloc(1, sizeof(cli_state));
+    cli_settings_read(&S->env); /* on every call: in-process callers change the environment between runs */
+    S->insert_printed = insert_printed;
+    S->force_serial = force_serial;
+    pthread_mutex_init(&S->fdev_mu, NULL);
+    if (S->env.segv_trace) cli_trace_fatal_signals(0);
+    setlinebuf(stdout);
+    if (force_serial && S->env.verbose) printf("reading the BAM serially\n");
+    S->t_cli0 = clock_gettime_s();
+    S->t_load = since_process_start();
+    fp_sampler fps = {0};
+    int ret = cli_parse(S, argc, argv);
+    if (ret < 0) {
+        ret = 1;
+        if (cli_open_bam(S) == 0 && cli_open_fasta(S, &fps) == 0 && cli_candidates(S) == 0) {
+            cli_name_outputs(S);
+            ret = reads_serially(S) ? run_serial(S) : run_streamed(S);
+            cli_report(S, &fps);
+        }
+        cli_release(S, &fps);
+    }
+    pthread_mutex_destroy(&S->fdev_mu);
     free(S);
     return ret;
 }
 
 int grom_cli_main(int argc, char **argv) {
-    t_insert_printed = 0;
-    int rc = cli_run(argc, argv, 0);
-    if (rc == CLI_FALLBACK) {
-        if (getenv("GROM_VERBOSE")) printf("reading the BAM serially\n");
-        rc = cli_run(argc, argv, 1);
-    }
+    int insert_printed = 0;
+    int rc = cli_run(argc, argv, 0, &insert_printed);
+    if (rc == CLI_FALLBACK) rc = cli_run(argc, argv, 1, &insert_printed); /* the streamed path could not be used */
     return rc;
 }

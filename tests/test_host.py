@@ -479,3 +479,27 @@ def test_c_child_plans_match_p(datadir):
     r = subprocess.run([GROM_BIN, "-i", bam, "-r", fa, "-o", "cr.vcf", "-c", "1,1,100000,200000"], cwd=str(datadir),
                        capture_output=True, text=True, env=dict(os.environ, GROM_PLAN_ONLY="1"))
     assert r.returncode != 0 and "sub-region" in r.stdout
+
+
+def test_settings_are_read_again_on_every_call(datadir, capfd):
+    """The CLI reads its GROM_* knobs at the start of every run and keeps
+    nothing between the runs of one process (the Python binding calls
+    grom_cli_main again and again): a run with GROM_CHROMS=chr2 plans one
+    chromosome, the next run of the same process, without it, plans all three,
+    exactly as a fresh process does."""
+    import grom_amd
+    bam, fa = synth(datadir, "three_chr", CASES["three_chr"])
+    args = ["-i", bam, "-r", fa, "-o", "reread.vcf"]
+
+    def plans(extra):
+        capfd.readouterr()
+        rc = grom_amd.cli_main(args, env=dict(extra, GROM_PLAN_ONLY="1", GROM_FILEDATE="20260101"), cwd=str(datadir))
+        assert rc == 0, grom_amd.last_error()
+        return sorted(l for l in capfd.readouterr().out.splitlines() if l.startswith("plan "))
+
+    one = plans({"GROM_CHROMS": "chr2"})
+    three = plans({})
+    assert len(one) == 1 and one[0].startswith("plan chr2 "), one
+    assert len(three) == 3 and one[0] in three, three
+    fresh = run(GROM_BIN, args, str(datadir), {"GROM_PLAN_ONLY": "1"})
+    assert three == sorted(l for l in fresh.stdout.splitlines() if l.startswith("plan "))

@@ -12,8 +12,10 @@
  *                        checked against a linear scan
  *   fmt <n>              the SNV row formatter against snprintf (snvfmt.cpp)
  *   synth <len>          one synthetic chromosome batch (synth.c, hostapi.c)
- *   ctx                  the translocation post-pass (grom_main.c) on a few
+ *   ctx                  the translocation post-pass (ctxpost.c) on a few
  *                        raw CTX rows
+ *   settings             the CLI's GROM_* knobs as cli_settings_read takes
+ *                        them from the environment, one "field=value" a line
  *   inflate <bam>        the device BGZF inflater's host twin against zlib on
  *                        every block (inflate_host.cpp)
  *   fasta <fa|fa.gz>     the FASTA host code: BGZF detection, the host inflate
@@ -38,6 +40,7 @@
 #include <string.h>
 
 #include "../include/grom_amd.h"
+#include "../grom_amd/csrc/cli_settings.h"
 
 static int cmd_bai(const char *bam, int64_t n) {
     if (grom_bai_build(bam) != 0) {
@@ -100,6 +103,27 @@ static int cmd_ctx(void) {
     printf("ctx post-pass: rc %d, %lld bytes\n", rc, (long long)out.ctx_len);
     grom_out_free(&out);
     return rc < 0;
+}
+
+static int cmd_settings(void) {
+    cli_settings s;
+    cli_settings_read(&s);
+#define FLAG(f) printf(#f "=%d\n", s.f)
+#define TEXT(f) printf(#f "=%s\n", s.f ? s.f : "(unset)")
+    FLAG(plan_only); FLAG(verbose); FLAG(fasta_serial); FLAG(segv_trace); FLAG(no_warm); FLAG(stage_digest);
+    FLAG(copy_stats); FLAG(no_ctx_prepare); FLAG(par_free); FLAG(cli_process); FLAG(exit_handlers); FLAG(p_serial);
+    FLAG(serial_decode); FLAG(build_index); FLAG(device_decode); FLAG(fasta_device);
+    TEXT(dump); TEXT(vcf_segs); TEXT(ctx_raw); TEXT(chroms); TEXT(filedate);
+    FLAG(has_seed);
+    printf("seed=%u\n", (unsigned)s.seed);
+    FLAG(device); FLAG(devices); FLAG(scans_per_gpu); FLAG(stages); FLAG(fasta_threads);
+    FLAG(has_decode_threads); FLAG(decode_threads); FLAG(n_worker_devices);
+#undef FLAG
+#undef TEXT
+    printf("worker_devices=");
+    for (int i = 0; i < s.n_worker_devices; i++) printf(i ? ",%d" : "%d", s.worker_devices[i]);
+    printf("\n");
+    return 0;
 }
 
 int grom_sv_rows_replay(const char *path); /* svcall.cpp test hook (sv.h) */
@@ -211,7 +235,7 @@ static int cmd_svrows(int n, char **paths) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: san_driver cli|bai|fmt|synth|ctx|svrows|cnvhost|inflate|fasta ...\n");
+        fprintf(stderr, "usage: san_driver cli|bai|fmt|synth|ctx|settings|svrows|cnvhost|inflate|fasta ...\n");
         return 2;
     }
     if (!strcmp(argv[1], "cli")) return grom_cli_main(argc - 1, argv + 1);
@@ -219,6 +243,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "fmt") && argc >= 3) return cmd_fmt(atoll(argv[2]));
     if (!strcmp(argv[1], "synth") && argc >= 3) return cmd_synth(atoll(argv[2]));
     if (!strcmp(argv[1], "ctx")) return cmd_ctx();
+    if (!strcmp(argv[1], "settings")) return cmd_settings();
     if (!strcmp(argv[1], "svrows") && argc >= 3) return cmd_svrows(argc - 2, argv + 2);
     if (!strcmp(argv[1], "cnvhost") && argc >= 3) return cmd_cnvhost(argc - 2, argv + 2);
     if (!strcmp(argv[1], "inflate") && argc >= 3) return cmd_inflate(argv[2]);
