@@ -2,100 +2,25 @@
 the host builder's (grom_bai_build, pinned by test_bai.py), byte for byte.
 
 The generator starts a new block rather than split a record, starts every
-chromosome on a new block and writes no unplaced records, so a helper here
-(zlib and struct only) inflates a generated BAM, may add records built in
-Python, and deflates the stream again into BGZF blocks whose payload sizes
-cycle through 997, 1, 4093, 65280, 37 bytes, with an empty block after the 5th
-and the 200th block and the EOF block last: records and their 36-byte headers
-straddle blocks, record ends land on block ends and empty blocks sit mid-file."""
+chromosome on a new block and writes no unplaced records, so a helper
+(tests/_handmade.py, zlib and struct only) inflates a generated BAM, may add
+records built in Python, and deflates the stream again into BGZF blocks whose
+payload sizes cycle through 997, 1, 4093, 65280, 37 bytes, with an empty block
+after the 5th and the 200th block and the EOF block last: records and their
+36-byte headers straddle blocks, record ends land on block ends and empty
+blocks sit mid-file."""
 import ctypes as C
 import os
 import shutil
 import struct
 import subprocess
-import zlib
 
 import pytest
 
+from _handmade import EMPTY_AFTER, _header_len, _inflate, _rec, _records, _reblock
 from _util import CASES, GROM_BIN, run_grom, synth
 
-PAYLOADS = (997, 1, 4093, 65280, 37)
-EMPTY_AFTER = (5, 200)
 _cache = {}
-
-
-def _inflate(path):
-    d = open(path, "rb").read()
-    out, o = [], 0
-    while o < len(d):
-        assert d[o:o + 4] == b"\x1f\x8b\x08\x04"
-        xlen, = struct.unpack_from("<H", d, o + 10)
-        bsize = None
-        x = o + 12
-        while x < o + 12 + xlen:
-            si1, si2, slen = struct.unpack_from("<BBH", d, x)
-            if (si1, si2, slen) == (66, 67, 2):
-                bsize, = struct.unpack_from("<H", d, x + 4)
-            x += 4 + slen
-        out.append(zlib.decompress(d[o + 12 + xlen:o + bsize + 1 - 8], -15))
-        o += bsize + 1
-    return b"".join(out)
-
-
-def _block(payload):
-    c = zlib.compressobj(1, zlib.DEFLATED, -15)
-    z = c.compress(payload) + c.flush()
-    assert len(z) + 26 <= 65536
-    return (struct.pack("<4BI2BH2B2H", 0x1f, 0x8b, 8, 4, 0, 0, 0xff, 6, 66, 67, 2, len(z) + 25) + z +
-            struct.pack("<II", zlib.crc32(payload), len(payload)))
-
-
-def _reblock(stream, path):
-    """The stream as BGZF blocks of the cycling payload sizes; returns the
-    number of blocks that hold data."""
-    blocks, o, k = [], 0, 0
-    while o < len(stream):
-        n = PAYLOADS[k % len(PAYLOADS)]
-        blocks.append(_block(stream[o:o + n]))
-        o += n
-        k += 1
-        if k in EMPTY_AFTER:
-            blocks.append(_block(b""))
-    blocks.append(_block(b""))  # the EOF block
-    open(path, "wb").write(b"".join(blocks))
-    return k
-
-
-def _header_len(s):
-    assert s[:4] == b"BAM\x01"
-    l_text, = struct.unpack_from("<i", s, 4)
-    o = 8 + l_text
-    n_ref, = struct.unpack_from("<i", s, o)
-    o += 4
-    for _ in range(n_ref):
-        ln, = struct.unpack_from("<i", s, o)
-        o += 4 + ln + 4
-    return o, n_ref
-
-
-def _records(s, o):
-    """(offset, length with block_size, tid, pos) of every record from o on."""
-    out = []
-    while o < len(s):
-        bs, tid, pos = struct.unpack_from("<iii", s, o)
-        out.append((o, 4 + bs, tid, pos))
-        o += 4 + bs
-    assert o == len(s)
-    return out
-
-
-def _rec(tid, pos, name, flag, cigar=(), l_seq=0, mapq=30):
-    qn = name + b"\0"
-    cig = b"".join(struct.pack("<I", n << 4 | "MIDNSHP=X".index(op)) for n, op in cigar)
-    body = (struct.pack("<iiBBHHHiiii", tid, pos, len(qn), mapq, 4680, len(cigar), flag, l_seq, -1, -1, 0) + qn + cig +
-            bytes((l_seq + 1) // 2) + b"\xff" * l_seq)
-    return struct.pack("<i", len(body)) + body
-
 
 UNPLACED = [_rec(-1, -1, b"u%d" % i, 4 | 8, (), 20, 0) for i in range(3)]
 

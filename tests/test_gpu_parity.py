@@ -92,8 +92,6 @@ def _names(datadir, tag):
     return sorted(f.split(".")[-2] for f in os.listdir(datadir) if f.startswith(tag + ".") and f.endswith(".cnt"))
 
 
-
-
 def _check_sv_records(datadir, o_dump, g_dump, ch):
     """Per-base breakpoint cluster state (rows A8/A9: every evaluated base with
     a DEL/DUP/INV/CTX cluster count or an occupied "other" slot -- counts,
@@ -112,6 +110,12 @@ def _check_sv_records(datadir, o_dump, g_dump, ch):
 
 def _check_counters(datadir, case, extra, tag, env_extra=None):
     bam, fa = synth(datadir, case, CASES[case])
+    _check_counters_files(datadir, bam, fa, case, extra, tag, env_extra)
+
+
+def _check_counters_files(datadir, bam, fa, case, extra, tag, env_extra=None):
+    """The comparison of _check_counters on any (bam, fa); `case` names the
+    generated case whose extra row-class checks apply (None: none)."""
     o_dump, g_dump = f"o_{tag}", f"g_{tag}"
     run_oracle(datadir, bam, fa, f"o_{tag}.vcf", extra, dump=str(datadir / o_dump))
     run_grom(datadir, bam, fa, f"g_{tag}.vcf", extra, dump=str(datadir / g_dump),
