@@ -14,6 +14,8 @@ HOST_OBJ = $(patsubst grom_amd/csrc/%.c,build/%.o,$(HOST_SRC)) build/snvfmt.o bu
 DEV_OBJ = build/scan.o build/cnv.o build/sv.o build/ddecode.o build/baidev.o build/fastadev.o build/gzipdev.o
 HDRS = include/grom_amd.h grom_amd/csrc/devmem.h grom_amd/csrc/devbuf.h grom_amd/csrc/scan_common.h grom_amd/csrc/bamio.h grom_amd/csrc/stream.h grom_amd/csrc/synth.h grom_amd/csrc/pdecode.h grom_amd/csrc/ddecode.h grom_amd/csrc/cnvcall.h grom_amd/csrc/cnv_bisect.h grom_amd/csrc/cli_settings.h grom_amd/csrc/ctxpost.h
 KHDRS = grom_amd/csrc/k_scan_tile.h grom_amd/csrc/device_common.h grom_amd/csrc/snvfmt.h
+# the BGZF checksum: the kernel's arithmetic (bgzfcrc.h, in ddecode.hip) and its host twin
+HOST_OBJ += build/bgzfcrc_host.o
 
 all: $(LIBDIR)/libgrom_amd.so $(BINDIR)/grom $(BINDIR)/grom_synth $(BINDIR)/gromc_binding oracle
 
@@ -44,6 +46,12 @@ build/scan.o: grom_amd/csrc/scan.hip $(HDRS) $(KHDRS) grom_amd/csrc/cnv.h grom_a
 build/ddecode.o: grom_amd/csrc/ddecode.hip grom_amd/csrc/ddecode.h grom_amd/csrc/inflate.h $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the BGZF checksum kernel's host twin (bgzfcrc.h's stages, the lanes as a loop) and the host file check
+build/ddecode.o: grom_amd/csrc/bgzfcrc.h
+build/bgzfcrc_host.o: grom_amd/csrc/bgzfcrc_host.cpp grom_amd/csrc/bgzfcrc.h grom_amd/csrc/inflate.h $(HDRS)
+	@mkdir -p build
+	$(CXX) -O2 -g -Wall -fPIC -std=c++17 -c $< -o $@
 
 # a missing BAM index built on the device (the decoder's inflater and upload path)
 build/baidev.o: grom_amd/csrc/baidev.hip grom_amd/csrc/ddecode.h $(HDRS)
@@ -185,6 +193,19 @@ $(SANDIR)/devbuf_check: tools/devbuf_check.cpp grom_amd/csrc/devbuf.h grom_amd/c
 $(SANDIR)/gzip_check: tools/gzip_check.cpp $(SANDIR)/gzip_host.o
 	@mkdir -p $(SANDIR)
 	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -std=c++17 $(SANFLAGS) $^ -lz -o $@
+
+# the BGZF checksum's host twin against zlib over the length / alignment grid,
+# and the host file check: no HIP, no device (tests/test_bgzf_crc_host.py)
+SAN_OBJ += $(SANDIR)/bgzfcrc_host.o
+$(SANDIR)/bgzfcrc_host.o: grom_amd/csrc/bgzfcrc_host.cpp grom_amd/csrc/bgzfcrc.h grom_amd/csrc/inflate.h $(HDRS)
+	@mkdir -p $(SANDIR)
+	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -fPIC -std=c++17 $(SANFLAGS) -c $< -o $@
+
+$(SANDIR)/crc_check: tools/crc_check.cpp $(SANDIR)/bgzfcrc_host.o
+	@mkdir -p $(SANDIR)
+	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -std=c++17 $(SANFLAGS) $^ -lz -o $@
+
+sanitize: $(SANDIR)/crc_check
 
 sanitize: $(SANDIR)/san_driver $(SANDIR)/grom_synth $(SANDIR)/devbuf_check $(SANDIR)/gzip_check
 

@@ -130,6 +130,11 @@ _SIGS = {
     "grom_bai_build_device": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int64)]),
     "grom_bai_summary": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64)]),
     "grom_bai_selftest": (C.c_int64, [C.c_char_p, C.c_int64, C.c_uint64, C.POINTER(C.c_int64)]),
+    # BGZF block checksums (bgzfcrc_host.cpp, ddecode.hip)
+    "grom_bgzf_verify": (C.c_int, [C.c_int]),
+    "grom_bgzf_check": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64]),
+    "grom_bgzf_check_device": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64]),
+    "grom_bgzf_crc_twin": (C.c_uint32, [C.c_char_p, C.c_int64, C.c_int64, C.c_uint32]),
     "grom_upload": (C.c_int, [C.c_int, C.POINTER(Chrom), C.POINTER(Reads), C.POINTER(Chrom), C.POINTER(Reads)]),
     "grom_synth_batch": (C.c_void_p, [C.c_int64, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_uint64,
                                       C.POINTER(Params)]),
@@ -226,6 +231,42 @@ def bai_build(bam: str, bai: str = None, device: int = 0) -> dict:
     rc = lib().grom_bai_build_device(os.fsencode(bam), None if bai is None else os.fsencode(bai), device, out)
     check(rc, "grom_bai_build_device")
     return dict(zip(BAI_BUILD_COUNTERS, (int(v) for v in out)))
+
+
+BGZF_CHECK_COUNTERS = ("blocks", "failing", "first_bad", "inflated_bytes", "pieces", "eof_marker", "device_us", "wall_us")
+
+
+def verify_bgzf_crc(on: "bool | None") -> "bool | None":
+    """Whether every reader of a BGZF file compares each inflated block's
+    CRC-32 with the block's trailer (True), does not (False) or follows
+    GROM_VERIFY_CRC at each open (None, the default).  Returns the previous
+    setting."""
+    prev = lib().grom_bgzf_verify(-1 if on is None else int(bool(on)))
+    return None if prev < 0 else bool(prev)
+
+
+def bgzf_check(path: str, device: "int | None" = None, max_bad: int = 4096) -> dict:
+    """Every block of the BGZF file `path` (a BAM, a bgzipped FASTA) inflated
+    and its CRC-32 compared: on the GPU `device`, or with None on the host
+    (one thread, zlib).  Returns the counters of BGZF_CHECK_COUNTERS
+    (eof_marker as a bool), `ok`, `bad_off` (up to max_bad failing blocks'
+    file offsets, ascending) and `error` (the library's message when a block
+    failed, else None).  Raises for a file that is not whole BGZF blocks and
+    for device errors."""
+    out = (C.c_int64 * 8)()
+    bad = (C.c_int64 * max(max_bad, 1))()
+    if device is None:
+        rc = lib().grom_bgzf_check(os.fsencode(path), out, bad, max_bad)
+    else:
+        rc = lib().grom_bgzf_check_device(os.fsencode(path), int(device), out, bad, max_bad)
+    res = dict(zip(BGZF_CHECK_COUNTERS, (int(v) for v in out)))
+    if rc != 0 and res["failing"] == 0:
+        check(rc, "grom_bgzf_check" if device is None else "grom_bgzf_check_device")
+    res["eof_marker"] = bool(res["eof_marker"])
+    res["ok"] = rc == 0
+    res["bad_off"] = [int(bad[i]) for i in range(min(res["failing"], max_bad))]
+    res["error"] = None if rc == 0 else last_error()
+    return res
 
 
 FASTA_NAME_LEN = 50

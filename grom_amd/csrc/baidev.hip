@@ -61,8 +61,11 @@ enum : uint32_t { IXB_RECORD = 1, IXB_UNSORTED = 2, IXB_TID = 4, IXB_LINCAP = 8,
 // the misc words on the device: 32-bit [0] bad bits, [1] blocks that did not
 // inflate, [2] block-table bounds, [3] chunks walked again; 64-bit (from byte
 // 32) [0] the chain's exit of the piece, [1] unplaced records; 32-bit (from
-// byte 64) the last record of the piece before, two copies of {valid, tid, pos, -}
+// byte 64) the last record of the piece before, two copies of {valid, tid, pos, -};
+// 32-bit (from byte 96) [0] blocks whose CRC-32 differs, [1] the lowest of them
+// in the piece (the check of GROM_VERIFY_CRC / grom_bgzf_verify)
 #define IX_MISC_BYTES 128
+#define IX_CRC_WORD 24
 
 // an unaligned word from two aligned ones (the caller checked p + 4 <= len; U
 // is readable for 64 bytes past len)
@@ -495,6 +498,10 @@ struct PieceIn {
 
 struct IxBuild {
     int device = 0, guess = 1;
+    bool verify = false;         // every piece's blocks against their CRC-32 (read once, in init)
+    const char *path = nullptr;  // ... and a mismatch names the file
+    double ms_crc = 0;
+    hipEvent_t ev_crc = nullptr;
     int64_t piece_bytes = (int64_t)3 << 30, comp_read = (int64_t)256 << 20;
     DdBgzfFile in;  // the BAM, read in whole blocks through two pinned ring buffers
     std::vector<int32_t> ref_len;
@@ -519,7 +526,7 @@ struct IxBuild {
     double ms_inflate = 0, ms_walk = 0, ms_reduce = 0;
     char err[512] = {0};
 
-    explicit IxBuild(const char *bam_path) : in(bam_path) {}
+    explicit IxBuild(const char *bam_path) : path(bam_path), in(bam_path) {}
     // the stream is drained and the decode context (whose copy stream reads
     // the ring buffers) freed here; the buffers and `in` free themselves after
     ~IxBuild() {
@@ -527,6 +534,7 @@ struct IxBuild {
         if (ctx) dd_ctx_free(ctx);
         for (int k = 0; k < 5; k++)
             if (ev[k]) (void)hipEventDestroy(ev[k]);
+        if (ev_crc) (void)hipEventDestroy(ev_crc);
         if (h_small) (void)hipHostFree(h_small);
         if (st) (void)hipStreamDestroy(st);
         for (bai_racc *a : racc) bai_racc_free(a);
@@ -604,6 +612,7 @@ struct IxBuild {
         const char *e = getenv("GROM_INDEX_PIECE_KB");
         if (e && atof(e) > 0) piece_bytes = std::max<int64_t>((int64_t)(atof(e) * 1024.0), 4096);
         if (getenv("GROM_INDEX_GUESS")) guess = atoi(getenv("GROM_INDEX_GUESS"));
+        verify = bgzf_verify_on() != 0;
         comp_read = std::min<int64_t>(comp_read, std::max<int64_t>(piece_bytes, 65536) + 65536);
         comp_read = std::min<int64_t>(comp_read, in.size);
         comp_read = std::max<int64_t>(comp_read, 4096);
@@ -611,6 +620,7 @@ struct IxBuild {
         if (!ctx) return fail(GROM_E_HIP, "device index build: no decode context on device %lld", device);
         IXK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         for (int k = 0; k < 5; k++) IXK(hipEventCreate(&ev[k]));
+        if (verify) IXK(hipEventCreate(&ev_crc));
         IXK((hipError_t)in.rings(comp_read, (size_t)(comp_read / 512 + 64)));
         IXK(hipHostMalloc((void **)&h_small, 32 * sizeof(int64_t), 0));
         IXG(misc, IX_MISC_BYTES);
@@ -728,6 +738,14 @@ struct IxBuild {
             if (dd_inflate_launch(st, d_comp, p.comp_len, P<DdBlock>(dblk), p.nblk, Up, 0, ulen, P<uint8_t>(status), m32 + 1,
                                   m32 + 2, tokb ? P<uint32_t>(tok) : nullptr, tokb ? tok.cap : 0))
                 return fail(GROM_E_HIP, "device index build: the inflate launch failed");
+            if (verify) {  // the piece's blocks against their CRC-32, before anything reads their bytes
+                IXK(hipEventRecord(ev_crc, st));
+                IXK(hipMemsetAsync(m32 + IX_CRC_WORD, 0, 4, st));
+                IXK(hipMemsetAsync(m32 + IX_CRC_WORD + 1, 0xff, 4, st));
+                if (dd_crc_launch(st, d_comp, p.comp_len, P<DdBlock>(dblk), p.nblk, Up, 0, ulen, P<uint8_t>(status),
+                                  m32 + IX_CRC_WORD, m32 + 2, m32 + IX_CRC_WORD + 1))
+                    return fail(GROM_E_HIP, "device index build: the CRC launch failed");
+            }
             IXK(hipEventRecord(ev[1], st));
             IXK(hipMemsetAsync(P<uint32_t>(sub_n) + nsub, 0, 4, st));
             hipLaunchKernelGGL(k_ix_sub, dim3((unsigned)nch), dim3(IX_T), 0, st, Up, ulen, start, nsub, guess, n_ref,
@@ -742,14 +760,25 @@ struct IxBuild {
             // the next piece is read and sent while this one is walked
             if ((rc = read_piece(s ^ 1)) != 0) return rc;
             IXK(hipStreamSynchronize(st));
+            if (verify && ((const uint32_t *)h_small)[IX_CRC_WORD]) {  // a hard error, the block named
+                const uint32_t bi = ((const uint32_t *)h_small)[IX_CRC_WORD + 1];
+                const int64_t foff = p.c0 + ((int64_t)bi < p.nblk ? p.blk[(size_t)bi].c_off : 0);
+                bgzf_crc_fail(path, foff);
+                dd_crc_message(err, (int)sizeof(err), path, foff);
+                return GROM_E_ARG;
+            }
             if ((rc = check_bad((const uint32_t *)h_small)) != 0) return rc;
             const int64_t exit_pos = h_small[4];
             const int64_t R = (int64_t)(uint32_t)h_small[16];
             if (exit_pos < start || exit_pos > ulen) return fail(GROM_E_ARG, "device index build: the record chain broke");
             {
                 float ms = 0;
-                (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+                (void)hipEventElapsedTime(&ms, ev[0], verify ? ev_crc : ev[1]);
                 ms_inflate += ms;
+                if (verify) {
+                    (void)hipEventElapsedTime(&ms, ev_crc, ev[1]);
+                    ms_crc += ms;
+                }
                 (void)hipEventElapsedTime(&ms, ev[1], ev[2]);
                 ms_walk += ms;
             }
@@ -868,10 +897,11 @@ extern "C" int grom_bai_build_device(const char *bam_path, const char *bai_path,
         IxBuild B(bam_path);
         B.device = device;
         int64_t hdr_len = 0;
+        bgzf_crc_error_clear();
         if (!B.in.fp || ix_read_header(bam_path, &hdr_len, B.ref_len) != 0) {
             char m[4400];
             snprintf(m, sizeof(m), "grom_bai_build_device: cannot read the BAM header of %s", bam_path);
-            grom_set_last_error(m);
+            grom_set_last_error(bgzf_crc_error() ? bgzf_crc_error() : m);  // (a verifying reader names the damaged block)
             return GROM_E_ARG;
         }
         B.n_ref = (int32_t)B.ref_len.size();
@@ -898,6 +928,9 @@ extern "C" int grom_bai_build_device(const char *bam_path, const char *bai_path,
                             "walk %.1f ms, reductions %.1f ms; wall %.1f ms\n",
                     (long long)B.n_rec, (long long)B.n_blk, (long long)B.n_piece, (long long)(B.piece_bytes >> 10),
                     B.ms_inflate, B.ms_walk, B.ms_reduce, wall / 1e3);
+        if (getenv("GROM_VERBOSE") && B.verify)
+            fprintf(stderr, "grom: device index build: block checksums %.1f ms (HIP events) next to the inflate's %.1f ms\n",
+                    B.ms_crc, B.ms_inflate);
     }
     return rc;
 }

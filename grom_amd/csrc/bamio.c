@@ -29,10 +29,51 @@ static void wr32(unsigned char *p, uint32_t v) {
     p[0] = v & 0xff; p[1] = (v >> 8) & 0xff; p[2] = (v >> 16) & 0xff; p[3] = v >> 24;
 }
 
+/* ---- the blocks' CRC-32 checked on request (grom_bgzf_verify, GROM_VERIFY_CRC) ---- */
+static int g_verify_mode = -1;
+
+int grom_bgzf_verify(int mode) {
+    const int prev = g_verify_mode;
+    if (mode >= -1 && mode <= 1) g_verify_mode = mode;
+    return prev;
+}
+
+int bgzf_verify_on(void) {
+    if (g_verify_mode >= 0) return g_verify_mode;
+    const char *e = getenv("GROM_VERIFY_CRC");
+    return e != NULL && atoi(e) != 0;
+}
+
+/* the first mismatch any reader met (the host's and the device's): kept until
+ * bgzf_crc_error_clear, so that a caller whose read loop takes an error for
+ * the end of the file still fails */
+static int g_crc_state; /* 0 none, 1 being written, 2 set */
+static char g_crc_msg[4400];
+
+void bgzf_crc_fail(const char *path, int64_t file_off) {
+    if (!__sync_bool_compare_and_swap(&g_crc_state, 0, 1)) return;
+    snprintf(g_crc_msg, sizeof(g_crc_msg), "BGZF block at file offset %lld of %s: CRC-32 mismatch", (long long)file_off,
+             path ? path : "the file");
+    __sync_synchronize();
+    g_crc_state = 2;
+}
+
+const char *bgzf_crc_error(void) {
+    __sync_synchronize();
+    return g_crc_state == 2 ? g_crc_msg : NULL;
+}
+
+void bgzf_crc_error_clear(void) {
+    g_crc_state = 0;
+    __sync_synchronize();
+}
+
 int bgzf_open_read(bgzf_reader *r, const char *path) {
     memset(r, 0, sizeof(*r));
     r->fp = fopen(path, "rb");
     if (!r->fp) return -1;
+    r->verify = bgzf_verify_on();
+    if (r->verify) r->path = strdup(path);
     r->blk = (unsigned char *)malloc(BGZF_MAX_BLOCK);
     r->cbuf = (unsigned char *)malloc(BGZF_MAX_BLOCK);
     if (!r->blk || !r->cbuf) return -1;
@@ -47,6 +88,7 @@ typedef struct {
     unsigned char *cbuf, *blk;
     int clen, len, rc, state;
     uint32_t isize;
+    int64_t coff; /* the block's file offset (a verifying reader) */
 } bgzf_slot;
 
 struct bgzf_mt {
@@ -54,14 +96,15 @@ struct bgzf_mt {
     bgzf_slot *slot;
     long head, tail; /* next slot to consume / to fill */
     int file_eof, file_err;
-    int stop;
+    int stop, verify;
     pthread_t *thr;
     pthread_mutex_t mu;
     pthread_cond_t work, done;
 };
 
-static int inflate_block(const unsigned char *cbuf, int clen, uint32_t isize, unsigned char *out) {
-    if (isize == 0) return 0;
+/* the block's bytes, or -1; with `verify` -2 when their CRC-32 is not the trailer's */
+static int inflate_block(const unsigned char *cbuf, int clen, uint32_t isize, unsigned char *out, int verify) {
+    if (isize == 0) return verify && rd32(cbuf + clen - 8) != 0 ? -2 : 0;
     z_stream zs;
     memset(&zs, 0, sizeof(zs));
     if (inflateInit2(&zs, -15) != Z_OK) return -1;
@@ -72,6 +115,7 @@ static int inflate_block(const unsigned char *cbuf, int clen, uint32_t isize, un
     int rc = inflate(&zs, Z_FINISH);
     inflateEnd(&zs);
     if (rc != Z_STREAM_END || zs.total_out != isize) return -1;
+    if (verify && (uint32_t)crc32(crc32(0L, Z_NULL, 0), out, isize) != rd32(cbuf + clen - 8)) return -2;
     return (int)isize;
 }
 
@@ -119,7 +163,7 @@ static void *bgzf_worker(void *arg) {
         if (m->stop) break;
         s->state = SLOT_BUSY;
         pthread_mutex_unlock(&m->mu);
-        const int rc = inflate_block(s->cbuf, s->clen, s->isize, s->blk);
+        const int rc = inflate_block(s->cbuf, s->clen, s->isize, s->blk, m->verify);
         pthread_mutex_lock(&m->mu);
         s->rc = rc;
         s->len = rc;
@@ -138,6 +182,7 @@ int bgzf_set_threads(bgzf_reader *r, int n) {
     if (!m) return -1;
     m->n_thr = 0; /* threads actually started (the only ones joined) */
     m->n_slot = 4 * n;
+    m->verify = r->verify;
     m->slot = (bgzf_slot *)calloc(m->n_slot, sizeof(bgzf_slot));
     m->thr = (pthread_t *)calloc(n, sizeof(pthread_t));
     int ok = m->slot && m->thr;
@@ -196,6 +241,7 @@ static int bgzf_mt_next(bgzf_reader *r) {
     while (!m->file_eof && !m->file_err && m->tail - m->head < m->n_slot) {
         bgzf_slot *s = &m->slot[m->tail % m->n_slot];
         pthread_mutex_unlock(&m->mu);
+        if (m->verify) s->coff = (int64_t)ftello(r->fp);
         const int rc = read_cblock(r->fp, s->cbuf, &s->clen, &s->isize);
         pthread_mutex_lock(&m->mu);
         if (rc <= 0) {
@@ -218,6 +264,7 @@ static int bgzf_mt_next(bgzf_reader *r) {
     while (s->state != SLOT_DONE) pthread_cond_wait(&m->done, &m->mu);
     m->head++;
     pthread_mutex_unlock(&m->mu);
+    if (s->rc == -2) bgzf_crc_fail(r->path, s->coff);
     if (s->rc < 0) return -1;
     /* hand the block over by swapping buffers (the slot is refilled later) */
     unsigned char *t = r->blk;
@@ -234,6 +281,7 @@ void bgzf_close_read(bgzf_reader *r) {
     if (r->fp) fclose(r->fp);
     free(r->blk);
     free(r->cbuf);
+    free(r->path);
     memset(r, 0, sizeof(*r));
 }
 
@@ -247,7 +295,8 @@ static int bgzf_next_block(bgzf_reader *r) {
     r->next_coff = (int64_t)ftell(r->fp);
     if (rc == 0) { r->eof = 1; return 0; }
     if (rc < 0) return -1;
-    const int n = inflate_block(r->cbuf, clen, isize, r->blk);
+    const int n = inflate_block(r->cbuf, clen, isize, r->blk, r->verify);
+    if (n == -2) bgzf_crc_fail(r->path, r->blk_coff);
     if (n < 0) return -1;
     r->blk_len = n;
     r->blk_off = 0;

@@ -56,6 +56,8 @@ typedef struct bgzf_reader {
     struct bgzf_mt *mt;     /* multi-threaded inflate (bgzf_set_threads), or NULL */
     int64_t blk_coff;       /* file offset of the current block (serial mode) */
     int64_t next_coff;      /* file offset of the block after it */
+    int verify;             /* every block's CRC-32 is compared with its trailer (bgzf_verify_on at the open) */
+    char *path;             /* ... and a mismatch names this file */
 } bgzf_reader;
 
 typedef struct bgzf_writer {
@@ -103,6 +105,16 @@ static inline int bam_seqi(const uint8_t *s, int i) { return (s[i >> 1] >> ((~i 
 /* htslib bam_nt16_rev_table: 4-bit code -> IUPAC char */
 extern const char grom_nt16_rev[16];
 
+/* Whether a reader opened now checks the blocks' CRC-32: grom_bgzf_verify's
+ * mode, or with -1 (the default) GROM_VERIFY_CRC.  A reader that checks fails
+ * its read (-1) at a block whose CRC-32 is not its trailer's and records
+ * "BGZF block at file offset N of PATH: CRC-32 mismatch" (bgzf_crc_fail: the
+ * first one is kept for bgzf_crc_error until bgzf_crc_error_clear). */
+int grom_bgzf_verify(int mode);
+int bgzf_verify_on(void);
+void bgzf_crc_fail(const char *path, int64_t file_off);
+const char *bgzf_crc_error(void);
+void bgzf_crc_error_clear(void);
 int bgzf_open_read(bgzf_reader *r, const char *path);
 void bgzf_close_read(bgzf_reader *r);
 /* read exactly n bytes; returns n, 0 at clean EOF, -1 on error/truncation */

@@ -47,7 +47,23 @@ size_t dd_inflate_tok_bytes(int64_t n_blk);
 int dd_inflate_launch(hipStream_t st, const uint8_t *d_comp, int64_t comp_cap, const DdBlock *d_blk, int64_t n_blk,
                       uint8_t *d_out, int64_t out_base, int64_t out_cap, uint8_t *d_status, uint32_t *d_bad,
                       uint32_t *d_bounds, uint32_t *d_tok, size_t tok_bytes);
+/* The same blocks' CRC-32 (k_bgzf_crc, one wave per block) after their inflate
+ * on `st`: the CRC of each block's out_len bytes compared on the device with
+ * the four bytes after its DEFLATE data (in_off + in_len + 8 <= comp_cap).  A
+ * block whose status is not 0 already is skipped; a CRC that differs sets
+ * status GI_E_CRC, counts in *d_bad and lowers *d_first_bad (start it at
+ * UINT32_MAX) to the block's index in d_blk; bit 0 of *d_bounds as above.
+ * d_out must be 16-byte aligned.  0, or -1 when the launch failed */
+int dd_crc_launch(hipStream_t st, const uint8_t *d_comp, int64_t comp_cap, const DdBlock *d_blk, int64_t n_blk,
+                  const uint8_t *d_out, int64_t out_base, int64_t out_cap, uint8_t *d_status, uint32_t *d_bad,
+                  uint32_t *d_bounds, uint32_t *d_first_bad);
 #endif
+/* a block's status after dd_crc_launch: its CRC-32 is not its trailer's */
+#define GI_E_CRC 10
+/* whether this open checks the blocks' CRC-32 (grom_bgzf_verify / GROM_VERIFY_CRC; bamio.c) */
+int bgzf_verify_on(void);
+/* "BGZF block at file offset N of PATH: CRC-32 mismatch" into err */
+void dd_crc_message(char *err, int errlen, const char *path, int64_t file_off);
 
 /* test hook: every whole block in the first max_bytes (<= 0: all) of a BAM
  * inflated on `device` and (check != 0) compared with zlib: the number of
@@ -65,6 +81,8 @@ void dd_ctx_free(dd_ctx *c);
 /* summed HIP-event times of the parsed runs: inflate, record walk, parse;
  * ms[3]: wall time of decode buffer growth so far (every context) */
 void dd_ctx_times(const dd_ctx *c, double ms[4]);
+/* ... and of the blocks' CRC-32 check, its own figure (0 when it is off) */
+double dd_ctx_crc_ms(const dd_ctx *c);
 /* record-walk sub-chunks whose guessed start was wrong (re-walked) / all */
 void dd_ctx_counts(const dd_ctx *c, int64_t *rewalked, int64_t *subchunks);
 /* the device buffers sized for the largest run (`ubytes` inflated bytes, a
@@ -127,6 +145,12 @@ typedef struct dd_run_req {
      * that run; its first piece is loaded while this run finishes */
     int (*next_cb)(void *arg, struct dd_run_req *next);
     void *next_arg;
+    /* every piece's blocks checked against their CRC-32 after the inflate
+     * (dd_crc_launch); a mismatch fails the run (-1) naming `path` and the
+     * block's offset in it, file_off + its c_off (next_cb fills these too) */
+    int verify_crc;
+    const char *path;
+    int64_t file_off;
 } dd_run_req;
 /* 0; -2 when the data contradicts the index plan (the CLI then reads
  * serially); -1.  *n_rec: the records walked (all of the run's with a stage) */

@@ -23,6 +23,7 @@
 #include "../../include/grom_amd.h"
 #include "ddecode.h"
 #include "devbuf.h"
+#include "bgzfcrc.h"
 #include "inflate.h"
 
 namespace {
@@ -246,6 +247,77 @@ extern "C" int dd_inflate_launch(hipStream_t st, const uint8_t *d_comp, int64_t 
     hipLaunchKernelGGL(k_inflate, dim3(grid), dim3(DD_LANES), GI_LANE_BYTES * DD_LANES + pad, st, d_comp, comp_cap,
                        d_blk, n_blk, d_out, out_base, out_cap, d_status, d_bad, d_bounds, 1);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- the blocks' CRC-32 (bgzfcrc.h) ----
+// One wave per block, four waves per workgroup over one set of tables in LDS,
+// a grid-stride loop over the blocks (the tables are built once per
+// workgroup).  Lane l runs bc_lane over the block's chunks l, l + 64, ...;
+// the lanes' values meet by shuffles and lane 0 finishes the CRC, reads the
+// four bytes after the block's DEFLATE data and compares.  A block the inflate
+// marked (status != 0) is skipped; one whose trailer or output lies outside
+// the buffers gets GI_E_BOUNDS; a CRC that differs gets GI_E_CRC, counts in
+// *n_bad and lowers *first_bad to its index.
+#define DD_CRC_WAVES 4
+__global__ void __launch_bounds__(DD_CRC_WAVES * BC_LANES) k_bgzf_crc(const uint8_t *__restrict__ comp, int64_t comp_cap,
+                                                                   const DdBlock *__restrict__ blk, int64_t n_blk,
+                                                                   const uint8_t *__restrict__ out, int64_t out_base,
+                                                                   int64_t out_cap, uint8_t *__restrict__ status,
+                                                                   uint32_t *__restrict__ n_bad,
+                                                                   uint32_t *__restrict__ bounds,
+                                                                   uint32_t *__restrict__ first_bad) {
+    __shared__ uint32_t tab[BC_DWORDS];
+    for (int s = 0; s < BC_STAGES; s++) {
+        bc_build_stage(s, (int)threadIdx.x, DD_CRC_WAVES * BC_LANES, tab);
+        __syncthreads();
+    }
+    const int lane = (int)threadIdx.x & (BC_LANES - 1), wave = (int)threadIdx.x / BC_LANES;
+    for (int64_t j = (int64_t)blockIdx.x * DD_CRC_WAVES + wave; j < n_blk; j += (int64_t)gridDim.x * DD_CRC_WAVES) {
+        if (status[j] != 0) continue;  // (uniform over the wave)
+        const DdBlock b = blk[j];
+        const int64_t o = b.out_off - out_base;
+        if (!dd_blk_inb(b, o, comp_cap, out_cap) || b.in_off + (int64_t)b.in_len + 8 > comp_cap) {
+            if (lane == 0) {
+                status[j] = (uint8_t)GI_E_BOUNDS;
+                atomicAdd(n_bad, 1u);
+                atomicOr(bounds, 1u);
+                atomicMin(first_bad, (uint32_t)j);
+            }
+            continue;
+        }
+        uint32_t v = bc_lane(out, out_cap, o, b.out_len, lane, tab);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v ^= (uint32_t)__shfl_xor((int)v, d, 64);
+        if (lane == 0) {
+            const uint32_t crc = bc_combine(v, out, out_cap, o, b.out_len, tab);
+            const uint8_t *t = comp + b.in_off + b.in_len;
+            const uint32_t want = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+            if (crc != want) {
+                status[j] = (uint8_t)GI_E_CRC;
+                atomicAdd(n_bad, 1u);
+                atomicMin(first_bad, (uint32_t)j);
+            }
+        }
+    }
+}
+
+extern "C" int dd_crc_launch(hipStream_t st, const uint8_t *d_comp, int64_t comp_cap, const DdBlock *d_blk, int64_t n_blk,
+                             const uint8_t *d_out, int64_t out_base, int64_t out_cap, uint8_t *d_status, uint32_t *d_bad,
+                             uint32_t *d_bounds, uint32_t *d_first_bad) {
+    if (n_blk <= 0) return 0;
+    // (the chunk loads are 16-byte loads at multiples of 16 from d_out)
+    if (((uintptr_t)d_out & 15) != 0) return -1;
+    const unsigned grid = (unsigned)std::min<int64_t>((n_blk + DD_CRC_WAVES - 1) / DD_CRC_WAVES, 1024);
+    hipLaunchKernelGGL(k_bgzf_crc, dim3(grid), dim3(DD_CRC_WAVES * BC_LANES), 0, st, d_comp, comp_cap, d_blk, n_blk, d_out,
+                       out_base, out_cap, d_status, d_bad, d_bounds, d_first_bad);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// "BGZF block at file offset N of PATH: CRC-32 mismatch" (every reader's wording)
+extern "C" void dd_crc_message(char *err, int errlen, const char *path, int64_t file_off) {
+    if (err && errlen > 0)
+        snprintf(err, (size_t)errlen, "BGZF block at file offset %lld of %s: CRC-32 mismatch", (long long)file_off,
+                 path ? path : "the file");
 }
 
 // ---- BGZF block table of a byte range (host) ----
@@ -1281,7 +1353,7 @@ struct RunSlotBufs {
 };
 struct RunSlot : RunSlotBufs {
     hipStream_t st = nullptr;
-    hipEvent_t ev[3] = {};
+    hipEvent_t ev[4] = {};       // before the inflate, after it, after the walk; [3] after the CRC check (when on)
     int64_t *h_small = nullptr;  // pinned, mapped: k_piece_summary writes it
     int64_t *d_small = nullptr;  // its device address
     bool misc_clean = false;     // misc's flag words are zero (k_piece_summary clears them)
@@ -1343,7 +1415,7 @@ struct dd_ctx : DdCtxBufs {
     int64_t *h_small = nullptr;  // pinned: totals and scalars
     uint8_t *h_aux = nullptr;    // pinned: packed split-read candidate records
     size_t h_aux_cap = 0;
-    float ms_inflate = 0, ms_walk = 0, ms_parse = 0;
+    float ms_inflate = 0, ms_walk = 0, ms_parse = 0, ms_crc = 0;
     int64_t n_rewalk = 0, n_sub = 0;  // record-walk sub-chunks re-walked by the verifying lane / all
     int cp_cap = CP_R;  // copy tiles staged in LDS up to this many reads (GROM_TEST_CP_UNSTAGED: 0, tests)
     int ws_guess = 1;  // record-start guesses: 1 plausible headers, 0 none, 2 sub-chunk starts (GROM_WS_GUESS, tests)
@@ -1451,7 +1523,7 @@ static dd_ctx *dd_ctx_make(int device) {
     for (int k = 0; k < DD_RSLOTS; k++) {
         RunSlot &r = c->rs[k];
         if (dd_stream_new(&r.st) != hipSuccess) r.st = nullptr;
-        for (int e = 0; e < 3; e++) (void)hipEventCreate(&r.ev[e]);
+        for (int e = 0; e < 4; e++) (void)hipEventCreate(&r.ev[e]);
         if (hipHostMalloc((void **)&r.h_small, 16 * sizeof(int64_t), hipHostMallocMapped) != hipSuccess ||
             hipHostGetDevicePointer((void **)&r.d_small, r.h_small, 0) != hipSuccess)
             r.h_small = nullptr;
@@ -1481,7 +1553,7 @@ extern "C" void dd_ctx_free(dd_ctx *c) {
         if (c->pev[k]) (void)hipEventDestroy(c->pev[k]);
         RunSlot &r = c->rs[k];
         if (r.st) (void)hipStreamSynchronize(r.st);
-        for (int e = 0; e < 3; e++)
+        for (int e = 0; e < 4; e++)
             if (r.ev[e]) (void)hipEventDestroy(r.ev[e]);
         if (r.h_small) (void)hipHostFree(r.h_small);
         if (r.st) (void)hipStreamDestroy(r.st);
@@ -1507,6 +1579,8 @@ extern "C" void dd_ctx_times(const dd_ctx *c, double *ms) {
     ms[2] = c->ms_parse;
     ms[3] = (double)g_dgrow_ns.load() / 1e6;
 }
+
+extern "C" double dd_ctx_crc_ms(const dd_ctx *c) { return c->ms_crc; }
 
 extern "C" void dd_ctx_counts(const dd_ctx *c, int64_t *rewalked, int64_t *subchunks) {
     *rewalked = c->n_rewalk;
@@ -1833,6 +1907,21 @@ static int issue_piece(dd_ctx *c, const dd_run_req *q, const Piece &pc, int k, d
         return -1;
     }
     DCK(hipEventRecord(r.ev[1], ls));
+    if (q->verify_crc) {
+        // the piece's blocks against their CRC-32, on the piece's stream: the
+        // count and the lowest failing block (misc words 16, 17) to the slot's
+        // pinned words 8, 9, read with the piece's summary
+        DCK(hipMemsetAsync(rb + 16, 0, 4, ls));
+        DCK(hipMemsetAsync(rb + 17, 0xff, 4, ls));
+        if (dd_crc_launch(ls, P<uint8_t>(c->dcomp[q->slot]), q->comp_len, P<DdBlock>(c->rblk[q->slot]) + pc.bf,
+                          pc.bl - pc.bf + 1, P<uint8_t>(r.U), pc.base, pc.pbytes, P<uint8_t>(r.status), rb + 16, rb + 5,
+                          rb + 17)) {
+            if (err) snprintf(err, (size_t)errlen, "CRC launch failed");
+            return -1;
+        }
+        DCK(hipMemcpyAsync((uint32_t *)r.h_small + 8, rb + 16, 8, hipMemcpyDeviceToHost, ls));
+        DCK(hipEventRecord(r.ev[3], ls));
+    }
     const int64_t nch = pc.cb - pc.ca;
     const int64_t *Sp = P<int64_t>(c->rS[q->slot]) + pc.ca;
     hipLaunchKernelGGL(k_walk_sub, dim3((unsigned)nch), dim3(WS_T), 0, ls, P<uint8_t>(r.U), Sp, pc.base, nch, q->tid,
@@ -1993,6 +2082,13 @@ static int run_decode(dd_ctx *c, const dd_run_req *q, dd_parse_out *po, int64_t 
             fprintf(stderr, "grom: %s\n", err ? err : "device decode: bounds");
             return -1;
         }
+        if (q->verify_crc && hs[8]) {  // a hard error: another reader would only meet the same bytes
+            const int64_t bi = pc.bf + (int64_t)hs[9];
+            const int64_t foff = q->file_off + (bi >= 0 && bi < q->nblk ? q->blk[bi].c_off : 0);
+            bgzf_crc_fail(q->path, foff);
+            dd_crc_message(err, errlen, q->path, foff);
+            return -1;
+        }
         if (hs[3]) {
             if (err) snprintf(err, (size_t)errlen, "device inflate: %u blocks failed", hs[3]);
             return -2;
@@ -2013,10 +2109,12 @@ static int run_decode(dd_ctx *c, const dd_run_req *q, dd_parse_out *po, int64_t 
             DCK(hipEventSynchronize(r.ev[2]));
         }
         {
-            float a = 0, b = 0;
+            float a = 0, b = 0, x = 0;
             (void)hipEventElapsedTime(&a, r.ev[0], r.ev[1]);
-            (void)hipEventElapsedTime(&b, r.ev[1], r.ev[2]);
+            if (q->verify_crc) (void)hipEventElapsedTime(&x, r.ev[1], r.ev[3]);
+            (void)hipEventElapsedTime(&b, q->verify_crc ? r.ev[3] : r.ev[1], r.ev[2]);
             c->ms_inflate += a;
+            c->ms_crc += x;
             c->ms_walk += b;
         }
         DCK(hipStreamWaitEvent(st, r.ev[2], 0));
@@ -2333,5 +2431,204 @@ extern "C" int dd_stage_prefix(dd_ctx *c, grom_stage *stage, int32_t s0, int64_t
         return -1;
     *sk = c->h_small[0];
     *sd = c->h_small[1];
+    return 0;
+}
+
+// ===========================================================================
+// The file check (grom_bgzf_check_device): every block of a BGZF file, a BAM
+// or a bgzipped FASTA, inflated and its CRC-32 compared on the device.  The
+// file is read once (DdBgzfFile) in pieces of whole blocks that go through
+// the decode context's two compressed slots, the next piece read and copied
+// while this one is inflated and checked; nothing is carried across pieces.
+// The host twin is grom_bgzf_check (bgzfcrc_host.cpp).
+// ===========================================================================
+namespace {
+
+struct BgzfCheck {
+    DdBgzfFile in;
+    dd_ctx *ctx = nullptr;
+    hipStream_t st = nullptr;
+    hipEvent_t ev[3] = {};
+    DBuf U, dblk, status, tok, misc;
+    std::vector<DdBlock> blk[2];
+    int64_t nblk[2] = {0, 0}, comp_len[2] = {0, 0}, ubytes[2] = {0, 0}, c0[2] = {0, 0};
+    bool eof_marker[2] = {false, false};
+    std::vector<uint8_t> h_status;
+    std::vector<int64_t> bad;  // every failing block's file offset, in file order
+    int64_t piece_bytes = (int64_t)3 << 30, comp_read = (int64_t)256 << 20;
+    int64_t n_blk = 0, n_piece = 0, n_ubytes = 0;
+    bool last_is_eof = false;
+    double ms_inflate = 0, ms_crc = 0;
+    char err[4400] = {0};
+
+    explicit BgzfCheck(const char *path) : in(path) {}
+    ~BgzfCheck() {
+        if (st) (void)hipStreamSynchronize(st);
+        if (ctx) dd_ctx_free(ctx);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    int fail(int code, const char *fmt, long long a = 0, long long b = 0) {
+        snprintf(err, sizeof(err), fmt, a, b);
+        return code;
+    }
+#define BCK(x)                                                                                                       \
+    do {                                                                                                             \
+        hipError_t e_ = (x);                                                                                         \
+        if (e_ != hipSuccess) {                                                                                      \
+            snprintf(err, sizeof(err), "BGZF check: HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); \
+            return GROM_E_HIP;                                                                                       \
+        }                                                                                                            \
+    } while (0)
+#define BCG(b, bytes)                                                                                          \
+    do {                                                                                                       \
+        if ((b).grow(bytes)) return fail(GROM_E_NOMEM, "BGZF check: hipMalloc(%lld) failed", (long long)(bytes)); \
+    } while (0)
+
+    // the next piece's blocks read into ring buffer s and sent to compressed slot s
+    int read_piece(int s) {
+        static const uint8_t eof_block[28] = {0x1f, 0x8b, 0x08, 0x04, 0x00, 0x00, 0x00, 0x00, 0x00, 0xff, 0x06, 0x00, 0x42, 0x43,
+                                              0x02, 0x00, 0x1b, 0x00, 0x03, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00};
+        nblk[s] = 0;
+        c0[s] = in.off;
+        if (in.off >= in.size) return 0;
+        if (dd_comp_ring_wait(ctx, s) != 0) return fail(GROM_E_HIP, "BGZF check: the copy ring failed");
+        const int64_t nb = in.read(s, piece_bytes, &comp_len[s], &ubytes[s]);
+        if (nb == DD_READ_IO) return fail(GROM_E_ARG, "BGZF check: read error at byte %lld", (long long)in.off);
+        if (nb <= 0) return fail(GROM_E_ARG, "BGZF check: no whole BGZF block at byte %lld", (long long)in.off);
+        blk[s].assign(in.tab.begin(), in.tab.begin() + nb);
+        nblk[s] = nb;
+        const DdBlock &lb = blk[s][(size_t)nb - 1];
+        eof_marker[s] = comp_len[s] - lb.c_off == 28 && memcmp(in.ring[s] + lb.c_off, eof_block, 28) == 0;
+        char e2[512] = {0};
+        if (dd_comp_begin(ctx, s, comp_len[s], e2, sizeof(e2)) != 0 ||
+            dd_comp_chunk(ctx, s, s, in.ring[s], 0, comp_len[s], e2, sizeof(e2)) != 0 ||
+            dd_comp_end(ctx, s, comp_len[s], e2, sizeof(e2)) != 0) {
+            snprintf(err, sizeof(err), "BGZF check: %s", e2[0] ? e2 : "the upload failed");
+            return GROM_E_HIP;
+        }
+        return 0;
+    }
+
+    int run(int device) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess)
+            return fail(GROM_E_NODEV, "BGZF check: no device %lld (%lld visible)", device, ndev);
+        const char *e = getenv("GROM_CHECK_PIECE_KB");
+        if (e && atof(e) > 0) piece_bytes = std::max<int64_t>((int64_t)(atof(e) * 1024.0), 4096);
+        comp_read = std::min<int64_t>(comp_read, std::max<int64_t>(piece_bytes, 65536) + 65536);
+        comp_read = std::min<int64_t>(comp_read, in.size);
+        comp_read = std::max<int64_t>(comp_read, 4096);
+        ctx = dd_ctx_new(device);
+        if (!ctx) return fail(GROM_E_HIP, "BGZF check: no decode context on device %lld", device);
+        BCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        for (hipEvent_t &v : ev) BCK(hipEventCreate(&v));
+        BCK((hipError_t)in.rings(comp_read, (size_t)(comp_read / 512 + 64)));
+        BCG(misc, 64);
+        int rc = read_piece(0);
+        if (rc) return rc;
+        for (int64_t k = 0;; k++) {
+            const int s = (int)(k & 1);
+            const int64_t nb = nblk[s];
+            if (nb == 0) {
+                if (in.off < in.size) return fail(GROM_E_ARG, "BGZF check: no whole BGZF block at byte %lld", in.off);
+                break;
+            }
+            BCG(U, (size_t)ubytes[s] + 64);
+            BCG(dblk, sizeof(DdBlock) * (size_t)(nb + 1));
+            BCG(status, (size_t)nb + 16);
+            const size_t tokb = dd_inflate_tok_bytes(nb);
+            if (tokb) BCG(tok, tokb);
+            const uint8_t *d_comp = nullptr;
+            int64_t comp_cap = 0;
+            if (dd_comp_view(ctx, s, &d_comp, &comp_cap) != 0 || comp_cap < comp_len[s] || dd_comp_wait_on(ctx, s, (void *)st) != 0)
+                return fail(GROM_E_HIP, "BGZF check: compressed slot %lld is not filled", s);
+            uint32_t *m32 = P<uint32_t>(misc);  // [0] blocks that did not inflate, [1] bounds, [2] CRCs that differ, [3] the first
+            BCK(hipMemcpyAsync(dblk.p, blk[s].data(), sizeof(DdBlock) * (size_t)nb, hipMemcpyHostToDevice, st));
+            BCK(hipMemsetAsync(m32, 0, 12, st));
+            BCK(hipMemsetAsync(m32 + 3, 0xff, 4, st));
+            BCK(hipEventRecord(ev[0], st));
+            if (dd_inflate_launch(st, d_comp, comp_len[s], P<DdBlock>(dblk), nb, P<uint8_t>(U), 0, ubytes[s], P<uint8_t>(status),
+                                  m32, m32 + 1, tokb ? P<uint32_t>(tok) : nullptr, tokb ? tok.cap : 0))
+                return fail(GROM_E_HIP, "BGZF check: the inflate launch failed");
+            BCK(hipEventRecord(ev[1], st));
+            if (dd_crc_launch(st, d_comp, comp_len[s], P<DdBlock>(dblk), nb, P<uint8_t>(U), 0, ubytes[s], P<uint8_t>(status),
+                              m32 + 2, m32 + 1, m32 + 3))
+                return fail(GROM_E_HIP, "BGZF check: the CRC launch failed");
+            BCK(hipEventRecord(ev[2], st));
+            uint32_t hm[4] = {0, 0, 0, 0};
+            h_status.resize((size_t)nb);
+            BCK(hipMemcpyAsync(hm, m32, 16, hipMemcpyDeviceToHost, st));
+            BCK(hipMemcpyAsync(h_status.data(), status.p, (size_t)nb, hipMemcpyDeviceToHost, st));
+            // the next piece is read and sent while this one is checked
+            const int64_t this_c0 = c0[s];
+            const bool this_eof = eof_marker[s];
+            std::vector<DdBlock> &tb = blk[s];
+            if ((rc = read_piece(s ^ 1)) != 0) return rc;
+            BCK(hipStreamSynchronize(st));
+            if (hm[1]) return fail(GROM_E_HIP, "BGZF check: a block table outside the piece's buffers (piece %lld)", k);
+            if (hm[0] || hm[2])
+                for (int64_t i = 0; i < nb; i++)
+                    if (h_status[(size_t)i] != 0) bad.push_back(this_c0 + tb[(size_t)i].c_off);
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+            ms_inflate += ms;
+            (void)hipEventElapsedTime(&ms, ev[1], ev[2]);
+            ms_crc += ms;
+            n_piece++;
+            n_blk += nb;
+            n_ubytes += ubytes[s];
+            last_is_eof = this_eof;
+        }
+        return 0;
+    }
+};
+
+}  // namespace
+
+extern "C" int grom_bgzf_check_device(const char *path, int device, int64_t out[8], int64_t *bad_off, int64_t bad_cap) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (out) memset(out, 0, 8 * sizeof(int64_t));
+    if (out) out[2] = -1;
+    char m[4600];
+    if (!path) {
+        grom_set_last_error("BGZF check: no path");
+        return GROM_E_ARG;
+    }
+    BgzfCheck B(path);
+    if (!B.in.fp) {
+        snprintf(m, sizeof(m), "BGZF check: cannot open %s", path);
+        grom_set_last_error(m);
+        return GROM_E_ARG;
+    }
+    int rc = B.run(device);
+    const int64_t wall = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    const int64_t nbad = (int64_t)B.bad.size();
+    if (out) {
+        out[0] = B.n_blk;
+        out[1] = nbad;
+        out[2] = nbad ? B.bad[0] : -1;
+        out[3] = B.n_ubytes;
+        out[4] = B.n_piece;
+        out[5] = B.last_is_eof ? 1 : 0;
+        out[6] = (int64_t)((B.ms_inflate + B.ms_crc) * 1000.0);
+        out[7] = wall;
+    }
+    for (int64_t i = 0; bad_off && i < nbad && i < bad_cap; i++) bad_off[i] = B.bad[(size_t)i];
+    if (getenv("GROM_VERBOSE"))
+        fprintf(stderr, "grom: BGZF check: %lld blocks, %lld failing, %lld pieces of <= %lld KB; inflate %.3f ms, CRC-32 %.3f ms; "
+                        "wall %.1f ms\n",
+                (long long)B.n_blk, (long long)nbad, (long long)B.n_piece, (long long)(B.piece_bytes >> 10), B.ms_inflate,
+                B.ms_crc, wall / 1e3);
+    if (rc != 0) {
+        grom_set_last_error(B.err[0] ? B.err : "BGZF check failed");
+        return rc;
+    }
+    if (nbad) {
+        dd_crc_message(m, (int)sizeof(m), path, B.bad[0]);
+        grom_set_last_error(m);
+        return GROM_E_ARG;
+    }
     return 0;
 }

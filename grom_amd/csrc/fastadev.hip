@@ -42,6 +42,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "../../include/grom_amd.h"
+#include "bamio.h"
 #include "ddecode.h"
 #include "devbuf.h"
 #include "gzipdev.h"
@@ -463,7 +464,9 @@ int ingest(grom_fasta_dev *d, const char *path) {
     FAG(misc, 64);
     FAK(hipMemcpyAsync(dblk.p, all.data(), sizeof(DdBlock) * (size_t)nb, hipMemcpyHostToDevice, d->st));
     FAK(hipMemsetAsync(misc.p, 0, 64, d->st));
-    uint32_t *m32 = P<uint32_t>(misc);
+    uint32_t *m32 = P<uint32_t>(misc);  // [0] blocks that did not inflate, [1] bounds, [2] CRCs that differ, [3] the first
+    const bool verify = bgzf_verify_on() != 0;  // (read once per open)
+    if (verify) FAK(hipMemsetAsync(m32 + 3, 0xff, 4, d->st));
     tic(d);
     // One block per lane: a launch's time hardly depends on the number of
     // blocks, and the text is resident, so every block goes in one launch
@@ -477,11 +480,28 @@ int ingest(grom_fasta_dev *d, const char *path) {
         if (dd_inflate_launch(d->st, P<uint8_t>(comp), fsize, P<DdBlock>(dblk) + b0, b1 - b0, d->text, 0, total,
                               P<uint8_t>(status) + b0, m32, m32 + 1, tokb ? P<uint32_t>(tok) : nullptr, tokb ? tok.cap : 0))
             return d->fail(GROM_E_HIP, "device FASTA: the inflate launch failed");
+        if (verify && dd_crc_launch(d->st, P<uint8_t>(comp), fsize, P<DdBlock>(dblk) + b0, b1 - b0, d->text, 0, total,
+                                    P<uint8_t>(status) + b0, m32 + 2, m32 + 1, m32 + 3))
+            return d->fail(GROM_E_HIP, "device FASTA: the CRC launch failed");
         b0 = b1;
     }
     FAK(hipMemcpyAsync(d->h_small, misc.p, 64, hipMemcpyDeviceToHost, d->st));
     if (toc(d, &d->ms[1])) return GROM_E_HIP;
     const uint32_t *h32 = (const uint32_t *)d->h_small;
+    if (verify && h32[2]) {  // a hard error: the host reader would meet the same bytes
+        int64_t foff = -1;
+        if (per_launch == INT64_MAX) {
+            foff = h32[3] < (uint64_t)nb ? all[(size_t)h32[3]].c_off : -1;
+        } else {  // (launches of their own block ranges: the first block whose trailer differs, found on the host)
+            std::vector<uint8_t> hs((size_t)nb);
+            FAK(hipMemcpy(hs.data(), status.p, (size_t)nb, hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < nb && foff < 0; i++)
+                if (hs[(size_t)i] == GI_E_CRC) foff = all[(size_t)i].c_off;
+        }
+        bgzf_crc_fail(path, foff);
+        dd_crc_message(d->err, (int)sizeof(d->err), path, foff);
+        return GROM_E_ARG;
+    }
     if (h32[0] || h32[1]) return d->fail(GROM_E_ARG, "device FASTA: %lld BGZF blocks did not inflate", h32[0]);
     return 0;
 }

@@ -1531,6 +1531,11 @@ static void streamed_report(const streamed_run *R) {
                (long long)pc.records, (long long)pc.pieces, pc.threads, pc.libdeflate ? "libdeflate" : "zlib",
                pc.inflated_bytes / 1e9, pc.h2d_bytes / 1e9, pc.decode_thread_s, pc.inflate_s, pc.io_s, pc.upload_s, pc.wait_s,
                clock_gettime_s() - R->t_start);
+    if (pc.verify_crc && pc.device) /* (a line of its own: the lines above keep their form) */
+        printf("block checksums: every BGZF block's CRC-32 checked on the GPU, %.3f s (HIP events) next to the inflate's %.3f s\n",
+               pc.crc_ms / 1e3, pc.gpu_ms[0] / 1e3);
+    else if (pc.verify_crc)
+        printf("block checksums: every BGZF block's CRC-32 checked by the decoder threads\n");
 }
 
 /* phase 7: the outputs, before any device memory is freed (that is teardown).
@@ -1538,7 +1543,7 @@ static void streamed_report(const streamed_run *R) {
  * callers such as the Python binding): the process ends here */
 static void streamed_outputs(streamed_run *R) {
     cli_state *S = R->S;
-    const int good = !R->fallback && R->status == 0;
+    const int good = !R->fallback && R->status == 0 && !bgzf_crc_error();
     S->t_scans = clock_gettime_s();
     if (R->pool.vcf) fclose(R->pool.vcf);
     if (good) finish_outputs(S, &R->pool.ctx_all);
@@ -1944,7 +1949,15 @@ static int cli_run(int argc, char **argv, int force_serial, int *insert_printed)
 
 int grom_cli_main(int argc, char **argv) {
     int insert_printed = 0;
+    bgzf_crc_error_clear();
     int rc = cli_run(argc, argv, 0, &insert_printed);
-    if (rc == CLI_FALLBACK) rc = cli_run(argc, argv, 1, &insert_printed); /* the streamed path could not be used */
+    /* the streamed path could not be used -- but never after a block failed
+     * its CRC-32: the serial reader would meet the same bytes */
+    if (rc == CLI_FALLBACK && !bgzf_crc_error()) rc = cli_run(argc, argv, 1, &insert_printed);
+    if (bgzf_crc_error()) { /* (a reader's loop may have taken the error for the end of the file) */
+        fprintf(stderr, "grom: %s\n", bgzf_crc_error());
+        grom_set_last_error(bgzf_crc_error());
+        if (rc == 0 || rc == CLI_FALLBACK) rc = 1;
+    }
     return rc;
 }

@@ -266,7 +266,12 @@ void grom_batch_release(grom_batch_handle *h) {
 }
 
 /* ---------------- BAM index entry points ---------------- */
-int grom_bai_build(const char *bam_path) { return bai_build(bam_path) == 0 ? 0 : GROM_E_ARG; }
+int grom_bai_build(const char *bam_path) {
+    bgzf_crc_error_clear();
+    if (bai_build(bam_path) == 0) return 0;
+    if (bgzf_crc_error()) grom_set_last_error(bgzf_crc_error()); /* (a verifying reader: the damaged block named) */
+    return GROM_E_ARG;
+}
 
 int grom_bai_summary(const char *bai_path, int64_t out[5]) {
     bai_index idx;

@@ -117,6 +117,9 @@ typedef struct {
     pd_inflater inf;
     int64_t inflated, compressed;
     double t_inflate, t_io;
+    int verify;          /* every block's CRC-32 is compared with its trailer (the session's switch) */
+    int crc_bad;         /* ... and the block at crc_bad_off failed that */
+    int64_t crc_bad_off;
 } pd_reader;
 
 static int rd_fetch(pd_reader *r, int64_t off, int64_t need) {
@@ -191,6 +194,11 @@ static int rd_next_block(pd_reader *r) {
         if (rd_reserve(r, r->ub_len + isize + 64)) return -1;
         const double t0 = now_s();
         if (inf_block(&r->inf, h + 12 + xlen, (size_t)(blen - 12 - xlen - 8), r->ub + r->ub_len, isize)) return -1;
+        if (r->verify && (uint32_t)crc32(crc32(0L, Z_NULL, 0), r->ub + r->ub_len, isize) != ld32(h + blen - 8)) {
+            r->crc_bad = 1;
+            r->crc_bad_off = r->next_coff;
+            return -1;
+        }
         r->t_inflate += now_s() - t0;
         if (r->next_coff == r->stop_coff) {
             r->stop_at = r->ub_len + r->stop_uoff;
@@ -392,6 +400,8 @@ struct pd_session {
     int next_piece, head, abort, stop;
     char abort_msg[300];
     int abort_soft;        /* the index plan was contradicted: read serially */
+    int verify_crc;        /* every inflated block's CRC-32 is checked (bgzf_verify_on, read once in pd_open) */
+    char *bam_path;        /* ... and a mismatch names the file */
     /* buffers */
     pd_buf *free_bufs, *inflight_head, *inflight_tail;
     int n_bufs, max_bufs, buf_waiters;
@@ -433,6 +443,7 @@ struct pd_session {
     pthread_t *dw;
     int n_dw, dw_started;
     double c_gpu_ms[4];    /* inflate, record walk, parse (HIP events, summed); buffer growth (wall) */
+    double c_crc_ms;       /* the blocks' CRC-32 check (HIP events, summed) */
     int64_t c_reclaimed;   /* idle stage blocks freed for a waiting allocation */
     int64_t c_stats_only;  /* device mode: runs decoded for the statistics alone */
     int stats_given;       /* the insert statistics come from <bam>.mean (pd_stats_given) */
@@ -714,7 +725,10 @@ static int stat_push(pd_piece *p, int32_t ins, int32_t lq, int64_t m) {
 static int decode_piece(pd_session *s, pd_reader *r, pd_piece *p, pd_buf *b) {
     const pd_run *run = &s->runs[p->run];
     const char *target = (run->chrom >= 0 && s->plan[run->chrom].target_name) ? s->plan[run->chrom].target_name : "";
+    r->verify = s->verify_crc;
+    r->crc_bad = 0;
     if (rd_open(r, s->fd, s->file_size, p->vbeg, p->vend)) {
+        if (r->crc_bad) goto bad;
         snprintf(p->err, sizeof(p->err), "piece at voffset %llu: bad block", (unsigned long long)p->vbeg);
         return -1;
     }
@@ -837,6 +851,12 @@ static int decode_piece(pd_session *s, pd_reader *r, pd_piece *p, pd_buf *b) {
     p->m_total = m;
     return 0;
 bad:
+    if (r->crc_bad) { /* a hard error: the serial reader would only meet the same block */
+        bgzf_crc_fail(s->bam_path, r->crc_bad_off);
+        snprintf(p->err, sizeof(p->err), "BGZF block at file offset %lld of %s: CRC-32 mismatch", (long long)r->crc_bad_off,
+                 s->bam_path);
+        return -1;
+    }
     snprintf(p->err, sizeof(p->err), "piece [%llu, %llu) of target %d does not decode as records of that target",
              (unsigned long long)p->vbeg, (unsigned long long)p->vend, run->tid);
     return -2;
@@ -1861,6 +1881,8 @@ pd_session *pd_open(const char *bam_path, const bam_hdr *hdr, const pd_chrom_in 
     if (idx.n_ref != hdr->n_ref) FAIL("index has %d references, BAM header %d", idx.n_ref, hdr->n_ref);
     s->fd = open(bam_path, O_RDONLY);
     if (s->fd < 0) FAIL("cannot open BAM");
+    s->verify_crc = bgzf_verify_on();
+    s->bam_path = strdup(bam_path);
     {
         struct stat st;
         if (fstat(s->fd, &st) != 0) FAIL("cannot stat BAM");
@@ -2042,6 +2064,7 @@ fail:
     free(s->keep);
     free(s->want);
     free(s->runs);
+    free(s->bam_path);
     free(s->pieces);
     free(s->s_ins);
     free(s->s_lq);
@@ -2395,6 +2418,9 @@ static int dw_next_cb(void *arg, dd_run_req *nq) {
         nq->u_end = sl->u_end;
         nq->tid = r->tid;
         nq->count = r->count;
+        nq->verify_crc = w->s->verify_crc;
+        nq->path = w->s->bam_path;
+        nq->file_off = (int64_t)(r->vbeg >> 16);
         got = 1;
     }
     pthread_mutex_unlock(&w->mu);
@@ -2441,6 +2467,9 @@ static int dw_decode(dd_worker *w, int ri, int next, grom_stage *stage, int64_t 
     rq.ref_len = ref_len;
     rq.count = r->count;
     rq.stage = stage;
+    rq.verify_crc = s->verify_crc;
+    rq.path = s->bam_path;
+    rq.file_off = (int64_t)(r->vbeg >> 16);
     if (stats && !s->stats_done) {
         rq.stats_left = s->insert_cap - s->s_n;
         rq.min_mapq = s->min_mapq_stats;
@@ -2883,6 +2912,7 @@ static void *dw_main(void *arg) {
         pthread_mutex_lock(&s->mu);
         for (int q = 0; q < 3; q++) s->c_gpu_ms[q] += ms[q];
         s->c_gpu_ms[3] = ms[3];
+        s->c_crc_ms += dd_ctx_crc_ms(w->dd);
         int64_t rw = 0, sc = 0;
         dd_ctx_counts(w->dd, &rw, &sc);
         s->c_rewalk += rw;
@@ -3115,6 +3145,8 @@ void pd_get_counters(pd_session *s, pd_counters *c) {
     c->inflate_s = s->c_inflate_s;
     c->device = s->dev_mode;
     for (int q = 0; q < 4; q++) c->gpu_ms[q] = s->c_gpu_ms[q];
+    c->verify_crc = s->verify_crc;
+    c->crc_ms = s->c_crc_ms;
     c->rewalked = s->c_rewalk;
     c->subchunks = s->c_subchunks;
     c->io_s = s->c_io_s;
@@ -3202,6 +3234,7 @@ void pd_close(pd_session *s) {
     free(s->keep);
     free(s->want);
     free(s->runs);
+    free(s->bam_path);
     free(s->pieces);
     free(s->s_ins);
     free(s->s_lq);

@@ -119,6 +119,8 @@ typedef struct pd_counters {
     int64_t reclaimed;   /* idle stage blocks freed for allocations short of device memory */
     int dd_workers;      /* device mode: decode workers (all GPUs) */
     int64_t stats_only_runs; /* device mode: runs decoded for the insert statistics alone */
+    int verify_crc;      /* the blocks' CRC-32 is checked (GROM_VERIFY_CRC / grom_bgzf_verify at pd_open) */
+    double crc_ms;       /* device mode: the check's kernels (HIP events, summed), next to gpu_ms[0] */
 } pd_counters;
 void pd_get_counters(pd_session *s, pd_counters *c);
 void pd_close(pd_session *s);

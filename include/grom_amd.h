@@ -487,6 +487,34 @@ int grom_bai_summary(const char *bai_path, int64_t out[5]);
  * negative on error.  *visited gets the records the fetches returned. */
 int64_t grom_bai_selftest(const char *bam_path, int64_t n_queries, uint64_t seed, int64_t *visited);
 
+/* ---- BGZF block checksums (added within ABI 7: new calls only, nothing
+ * existing changes, GROM_AMD_ABI_VERSION stays 7) ---- */
+/* Whether every reader of a BGZF file (the BAM decoders on the host and on the
+ * device, the index builders, the BGZF FASTA readers) compares each inflated
+ * block's CRC-32 with the block's trailer: 1 yes, 0 no, -1 (the default) as
+ * GROM_VERIFY_CRC says at each open.  A mismatch fails the call or the run
+ * with "BGZF block at file offset N of PATH: CRC-32 mismatch"; nothing falls
+ * back to another reader.  Returns the previous mode. */
+int grom_bgzf_verify(int mode);
+/* Every block of a BGZF file (a BAM, a bgzipped FASTA) inflated and its CRC-32
+ * compared, whatever grom_bgzf_verify says.  grom_bgzf_check: the host, one
+ * thread, zlib's inflate and crc32.  grom_bgzf_check_device: on `device`, the
+ * file read once in pieces of whole blocks (GROM_CHECK_PIECE_KB inflated bytes
+ * each, default 3145728 = 3 GB), nothing carried across pieces.  out (may be
+ * NULL) = {blocks, failing blocks, the first failing block's file offset or
+ * -1, inflated bytes, pieces, 1 when the last block is the 28-byte EOF marker,
+ * device time (us, HIP events; 0 on the host), wall time (us)}; bad_off (may
+ * be NULL) takes up to bad_cap failing blocks' file offsets, ascending.  A
+ * block fails when it does not inflate to ISIZE bytes or its CRC-32 differs.
+ * 0 when none failed (a missing EOF marker is reported in out, not an error);
+ * GROM_E_ARG with the message above when one did, and for a file that is not
+ * whole BGZF blocks; GROM_E_NODEV, GROM_E_HIP, GROM_E_NOMEM. */
+int grom_bgzf_check(const char *path, int64_t out[8], int64_t *bad_off, int64_t bad_cap);
+int grom_bgzf_check_device(const char *path, int device, int64_t out[8], int64_t *bad_off, int64_t bad_cap);
+/* the CRC-32 of buf[off, off + n) by the device kernel's algorithm run on the
+ * host (the lanes as a loop; tests): every load stays inside buf[0, cap) */
+uint32_t grom_bgzf_crc_twin(const uint8_t *buf, int64_t cap, int64_t off, uint32_t n);
+
 /* ---- the reference FASTA read on the device (fastadev.hip):
  * plain text or BGZF (bgzip); the index (find_genome_length, GROM.c:1321-1428)
  * and the loader (GROM.c:21009-21045) give the host code's results bit for
