@@ -17,6 +17,11 @@ KHDRS = grom_amd/csrc/k_scan_tile.h grom_amd/csrc/device_common.h grom_amd/csrc/
 # the BGZF checksum: the kernel's arithmetic (bgzfcrc.h, in ddecode.hip) and its host twin
 HOST_OBJ += build/bgzfcrc_host.o
 
+# BGZF written on the device: the compressor's arithmetic (bgzfdef.h, in bgzfwrite.hip) and its host twin
+HOST_OBJ += build/bgzfdef_host.o
+DEV_OBJ += build/bgzfwrite.o
+DF_HDRS = grom_amd/csrc/bgzfdef.h grom_amd/csrc/bgzfwrite.h grom_amd/csrc/bgzfcrc.h grom_amd/csrc/inflate.h
+
 all: $(LIBDIR)/libgrom_amd.so $(BINDIR)/grom $(BINDIR)/grom_synth $(BINDIR)/gromc_binding oracle
 
 build/%.o: grom_amd/csrc/%.c $(HDRS)
@@ -50,6 +55,16 @@ build/ddecode.o: grom_amd/csrc/ddecode.hip grom_amd/csrc/ddecode.h grom_amd/csrc
 # the BGZF checksum kernel's host twin (bgzfcrc.h's stages, the lanes as a loop) and the host file check
 build/ddecode.o: grom_amd/csrc/bgzfcrc.h
 build/bgzfcrc_host.o: grom_amd/csrc/bgzfcrc_host.cpp grom_amd/csrc/bgzfcrc.h grom_amd/csrc/inflate.h $(HDRS)
+	@mkdir -p build
+	$(CXX) -O2 -g -Wall -fPIC -std=c++17 -c $< -o $@
+
+# the BGZF writer: the DEFLATE kernels, the piece pipeline, the C calls
+build/bgzfwrite.o: grom_amd/csrc/bgzfwrite.hip $(DF_HDRS) $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the compressor's host twin (bgzfdef.h's phases, the lanes as loops; no HIP)
+build/bgzfdef_host.o: grom_amd/csrc/bgzfdef_host.cpp $(DF_HDRS) $(HDRS)
 	@mkdir -p build
 	$(CXX) -O2 -g -Wall -fPIC -std=c++17 -c $< -o $@
 
@@ -117,12 +132,12 @@ oracle:
 # kernel tuning variants, loaded with GROM_AMD_LIB=...:
 #   make variant V=w4 VFLAGS=-DGROM_WAVES_PER_EU=4  ->  grom_amd/lib/variants/libgrom_amd_w4.so
 #   make variant V=q0 VFLAGS=-DGI_QUAD=0            (the inflater's bit reader)
-variant: $(HOST_OBJ) build/sv.o build/baidev.o build/fastadev.o build/gzipdev.o
+variant: $(HOST_OBJ) build/sv.o build/baidev.o build/fastadev.o build/gzipdev.o build/bgzfwrite.o
 	@mkdir -p build/variants $(LIBDIR)/variants
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c grom_amd/csrc/scan.hip -o build/variants/scan_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -ffp-contract=off -c grom_amd/csrc/cnv.hip -o build/variants/cnv_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c grom_amd/csrc/ddecode.hip -o build/variants/ddecode_$(V).o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(LIBDIR)/variants/libgrom_amd_$(V).so build/variants/scan_$(V).o build/variants/cnv_$(V).o build/sv.o build/variants/ddecode_$(V).o build/baidev.o build/fastadev.o build/gzipdev.o $(HOST_OBJ) -lz -lm
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(LIBDIR)/variants/libgrom_amd_$(V).so build/variants/scan_$(V).o build/variants/cnv_$(V).o build/sv.o build/variants/ddecode_$(V).o build/baidev.o build/fastadev.o build/gzipdev.o build/bgzfwrite.o $(HOST_OBJ) -lz -lm
 
 clean:
 	rm -rf build $(LIBDIR) $(BINDIR)
@@ -206,6 +221,20 @@ $(SANDIR)/crc_check: tools/crc_check.cpp $(SANDIR)/bgzfcrc_host.o
 	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -std=c++17 $(SANFLAGS) $^ -lz -o $@
 
 sanitize: $(SANDIR)/crc_check
+
+# the compressor's host twin against zlib's decoder over the length / content
+# grid, every buffer ending where its data ends, and the code-length builder
+# alone: no HIP, no device (tests/test_bgzf_write_host.py)
+SAN_OBJ += $(SANDIR)/bgzfdef_host.o
+$(SANDIR)/bgzfdef_host.o: grom_amd/csrc/bgzfdef_host.cpp $(DF_HDRS) $(HDRS)
+	@mkdir -p $(SANDIR)
+	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -fPIC -std=c++17 $(SANFLAGS) -c $< -o $@
+
+$(SANDIR)/deflate_check: tools/deflate_check.cpp $(SANDIR)/bgzfdef_host.o $(SANDIR)/bgzfcrc_host.o
+	@mkdir -p $(SANDIR)
+	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -std=c++17 $(SANFLAGS) $^ -lz -o $@
+
+sanitize: $(SANDIR)/deflate_check
 
 sanitize: $(SANDIR)/san_driver $(SANDIR)/grom_synth $(SANDIR)/devbuf_check $(SANDIR)/gzip_check
 

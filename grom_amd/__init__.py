@@ -135,6 +135,13 @@ _SIGS = {
     "grom_bgzf_check": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64]),
     "grom_bgzf_check_device": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64]),
     "grom_bgzf_crc_twin": (C.c_uint32, [C.c_char_p, C.c_int64, C.c_int64, C.c_uint32]),
+    # BGZF written on the device (bgzfwrite.hip; device -1: the host twin, bgzfdef_host.cpp)
+    "grom_bgzf_writer_open": (C.c_void_p, [C.c_char_p, C.c_int, C.c_char_p]),
+    "grom_bgzf_writer_write": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
+    "grom_bgzf_writer_close": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "grom_bgzf_compress": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int64)]),
+    "grom_bgzf_blocks": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.c_int64, C.c_int, C.c_char_p, C.c_int64,
+                                   C.POINTER(C.c_int64)]),
     "grom_upload": (C.c_int, [C.c_int, C.POINTER(Chrom), C.POINTER(Reads), C.POINTER(Chrom), C.POINTER(Reads)]),
     "grom_synth_batch": (C.c_void_p, [C.c_int64, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_uint64,
                                       C.POINTER(Params)]),
@@ -267,6 +274,87 @@ def bgzf_check(path: str, device: "int | None" = None, max_bad: int = 4096) -> d
     res["bad_off"] = [int(bad[i]) for i in range(min(res["failing"], max_bad))]
     res["error"] = None if rc == 0 else last_error()
     return res
+
+
+BGZF_WRITE_COUNTERS = ("blocks", "stored", "fixed", "dynamic", "literal_dynamic", "in_bytes", "out_bytes", "pieces",
+                       "device_us", "wall_us")
+BGZF_MAX_PAYLOAD = 65280
+
+
+class BgzfWriter:
+    """A BGZF file written through the GPU `device`'s DEFLATE compressor, or
+    with None through its host twin (the same bytes).  `gzi`: also bgzip's
+    <path>.gzi index.  Use as a context manager; `write(bytes)` may cut the
+    stream anywhere.  After the block, `stats` holds BGZF_WRITE_COUNTERS.  An
+    exception inside the block still closes the writer."""
+
+    def __init__(self, path: str, device: "int | None" = None, gzi: bool = True):
+        self.path, self.stats = path, None
+        self._h = lib().grom_bgzf_writer_open(os.fsencode(path), -1 if device is None else int(device),
+                                              os.fsencode(path + ".gzi") if gzi else None)
+        if not self._h:
+            raise RuntimeError(f"grom_bgzf_writer_open failed: {last_error()}")
+
+    def write(self, data: bytes) -> int:
+        if self._h is None:
+            raise ValueError("write to a closed BgzfWriter")
+        data = bytes(data)
+        check(lib().grom_bgzf_writer_write(self._h, data, len(data)), "grom_bgzf_writer_write")
+        return len(data)
+
+    def close(self) -> dict:
+        if self._h is not None:
+            out = (C.c_int64 * 10)()
+            h, self._h = self._h, None
+            rc = lib().grom_bgzf_writer_close(h, out)
+            self.stats = dict(zip(BGZF_WRITE_COUNTERS, (int(v) for v in out)))
+            check(rc, "grom_bgzf_writer_close")
+        return self.stats
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def bgzf_compress(src: str, dst: str, device: "int | None" = None, gzi: bool = True) -> dict:
+    """The file `src` as the BGZF file `dst` (and, with gzi, bgzip's
+    `dst`.gzi), compressed on the GPU `device` or with None by the host twin,
+    which writes the same bytes.  Returns BGZF_WRITE_COUNTERS."""
+    if gzi:
+        out = (C.c_int64 * 10)()
+        rc = lib().grom_bgzf_compress(os.fsencode(src), os.fsencode(dst), -1 if device is None else int(device), out)
+        check(rc, "grom_bgzf_compress")
+        return dict(zip(BGZF_WRITE_COUNTERS, (int(v) for v in out)))
+    with open(src, "rb") as f, BgzfWriter(dst, device, gzi=False) as w:
+        while True:
+            b = f.read(8 << 20)
+            if not b:
+                break
+            w.write(b)
+    return w.stats
+
+
+def bgzf_blocks(payloads, device: "int | None" = None, lead: int = 0) -> list:
+    """Test hook: every payload (bytes of at most 65280) as one BGZF block, all
+    in one launch on `device` (None: the host twin).  The payloads are laid out
+    back to back after `lead` bytes, so their start alignments vary."""
+    buf = bytes(lead) + b"".join(payloads)
+    offs, o = [lead], lead
+    for p in payloads:
+        o += len(p)
+        offs.append(o)
+    n = len(payloads)
+    cap = len(buf) + 31 * n + 64
+    dst = C.create_string_buffer(cap)
+    d_offs = (C.c_int64 * (n + 1))()
+    rc = lib().grom_bgzf_blocks(buf, (C.c_int64 * (n + 1))(*offs), n, -1 if device is None else int(device), dst, cap,
+                                d_offs)
+    check(rc, "grom_bgzf_blocks")
+    raw = dst.raw
+    return [raw[d_offs[i]:d_offs[i + 1]] for i in range(n)]
 
 
 FASTA_NAME_LEN = 50

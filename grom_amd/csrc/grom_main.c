@@ -11,6 +11,7 @@
  * are accepted and recorded.  The GROM_* environment knobs are read once per
  * run (cli_settings.c lists them); the translocation post-pass is ctxpost.c.
  */
+#define _GNU_SOURCE /* fopencookie: the rows' FILE over the BGZF writer (GROM_VCF_BGZF) */
 #include <dirent.h>
 #include <pthread.h>
 #include <stdio.h>
@@ -291,6 +292,11 @@ typedef struct {
      * the chromosome's end: the children -P n forks without -R). */
     int one_chrom, sub_child, sub_start, sub_end;
     char part_name[4096];
+    /* GROM_VCF_BGZF: the rows and the CTX file go out as BGZF (<name>.gz),
+     * compressed on the run's first device; what each close reported */
+    char gz_name[4100], ctx_gz_name[4100];
+    int64_t gz_rows[10], gz_ctx[10];
+    int gz_failed;
 } cli_state;
 
 static void plan_release_dref(cli_state *S, chrom_plan *c) {
@@ -909,10 +915,52 @@ static int passes_length(const cli_state *S, const chrom_plan *c) {
     return c->len > s0 + (long)S->P.overlap_mult * S->P.insert_max_size && c->len > 0 && c->len <= S->max_chr_len;
 }
 
+/* GROM_VCF_BGZF: a FILE whose bytes go to a BGZF writer on the run's first
+ * device (grom_bgzf_writer_*); fclose closes the writer, which
+ * frees its device memory, and keeps its counters in out[10] */
+typedef struct {
+    grom_bgzf_writer *w;
+    cli_state *S;
+    int64_t *out;
+} gz_cookie;
+
+static ssize_t gz_cookie_write(void *c, const char *buf, size_t n) {
+    gz_cookie *g = c;
+    if (grom_bgzf_writer_write(g->w, buf, (int64_t)n) != 0) { g->S->gz_failed = 1; return 0; }
+    return (ssize_t)n;
+}
+
+static int gz_cookie_close(void *c) {
+    gz_cookie *g = c;
+    const int rc = grom_bgzf_writer_close(g->w, g->out);
+    if (rc != 0) {
+        g->S->gz_failed = 1;
+        printf("Error writing BGZF output: %s\n", grom_last_error());
+    }
+    free(g);
+    return rc ? -1 : 0;
+}
+
+static FILE *gz_fopen(cli_state *S, const char *name, int with_gzi, int64_t *out) {
+    char gzi[4200];
+    snprintf(gzi, sizeof(gzi), "%s.gzi", name);
+    hip_ready(S);
+    gz_cookie *g = calloc(1, sizeof(*g));
+    g->S = S;
+    g->out = out;
+    g->w = grom_bgzf_writer_open(name, S->device, with_gzi ? gzi : NULL);
+    if (!g->w) { free(g); return NULL; }
+    const cookie_io_functions_t io = {NULL, gz_cookie_write, NULL, gz_cookie_close};
+    FILE *f = fopencookie(g, "w", io);
+    if (!f) { grom_bgzf_writer_close(g->w, NULL); free(g); return NULL; }
+    setvbuf(f, NULL, _IOFBF, 1 << 20);
+    return f;
+}
+
 /* the rows' file, under its header */
 static FILE *open_rows(cli_state *S) {
-    FILE *vcf = fopen(S->out_name, "w");
-    if (!vcf) { printf("Error opening file %s\n", S->out_name); return NULL; }
+    FILE *vcf = S->env.vcf_bgzf ? gz_fopen(S, S->gz_name, 1, S->gz_rows) : fopen(S->out_name, "w");
+    if (!vcf) { printf("Error opening file %s\n", S->env.vcf_bgzf ? S->gz_name : S->out_name); return NULL; }
     if (S->one_chrom < 0) { /* (-c: rows only, the parent wrote the header) */
         if (S->P.vcf == 1) header(vcf, S->fasta_name, 0, S->env.filedate);
         else tab_header(vcf, &S->P);
@@ -934,7 +982,7 @@ static void finish_outputs(cli_state *S, textbuf *ctx_all) {
     if (S->env.ctx_raw) write_file(S->env.ctx_raw, ctx_all); /* for a merge of several ranks' runs */
     /* CTX post-pass (GROM.c:22400-22770): pair the translocation rows of all
      * chromosomes with their mates and write them under the header */
-    FILE *ctx = fopen(S->ctx_name, "w");
+    FILE *ctx = S->env.vcf_bgzf ? gz_fopen(S, S->ctx_gz_name, 0, S->gz_ctx) : fopen(S->ctx_name, "w");
     if (ctx) {
         if (S->P.vcf == 1) header(ctx, S->fasta_name, 1, S->env.filedate);
         else /* the trimmed file's column header, GROM.c:22652-22700 */
@@ -944,6 +992,11 @@ static void finish_outputs(cli_state *S, textbuf *ctx_all) {
         ctx_postpass(ctx_all->p, ctx_all->len, &S->hdr, S->P.insert_max_size, S->P.lseq, S->P.vcf == 1, ctx);
         fclose(ctx);
     }
+    if (S->env.vcf_bgzf && !S->gz_failed)
+        printf("BGZF output (device %d): %s with %s.gzi, %lld blocks, %lld -> %lld bytes; %s, %lld blocks, %lld -> %lld bytes; "
+               "%.3f s on the device\n", S->device, S->gz_name, S->gz_name, (long long)S->gz_rows[0], (long long)S->gz_rows[5],
+               (long long)S->gz_rows[6], S->ctx_gz_name, (long long)S->gz_ctx[0], (long long)S->gz_ctx[5],
+               (long long)S->gz_ctx[6], (double)(S->gz_rows[8] + S->gz_ctx[8]) / 1e6);
 }
 
 /* rows of finished jobs, in chromosome order (caller holds pool.mu) */
@@ -1548,7 +1601,7 @@ static void streamed_outputs(streamed_run *R) {
     if (R->pool.vcf) fclose(R->pool.vcf);
     if (good) finish_outputs(S, &R->pool.ctx_all);
     S->t_outputs = clock_gettime_s();
-    if (!good || !S->env.cli_process) return;
+    if (!good || !S->env.cli_process || S->gz_failed) return;
     /* every scan has finished and the outputs are closed; the process's
      * device memory, streams and pinned buffers go with it (hipFree of
      * ~150 GB of stages and scratch, and the runtime's own teardown, are
@@ -1764,8 +1817,11 @@ static int cli_open_bam(cli_state *S) {
         snprintf(S->part_name, sizeof(S->part_name), "%s.%s-%d", S->out_name, S->hdr.ref_name[S->one_chrom], S->sub_child);
         S->out_name = S->part_name;
     } else {
-        FILE *probe = fopen(S->out_name, "w");
-        if (!probe) { printf("\nCould not open %s\n", S->out_name); return 1; }
+        /* (GROM_VCF_BGZF: the plain file is never created) */
+        snprintf(S->gz_name, sizeof(S->gz_name), "%s.gz", S->out_name);
+        const char *name = S->env.vcf_bgzf ? S->gz_name : S->out_name;
+        FILE *probe = fopen(name, "w");
+        if (!probe) { printf("\nCould not open %s\n", name); return 1; }
         fclose(probe);
     }
     return 0;
@@ -1871,6 +1927,7 @@ static void cli_name_outputs(cli_state *S) {
         snprintf(S->ctx_name, sizeof(S->ctx_name), "%.*s.ctx.vcf", (int)(ol - 4), S->out_name);
     else
         snprintf(S->ctx_name, sizeof(S->ctx_name), "%s.ctx", S->out_name);
+    snprintf(S->ctx_gz_name, sizeof(S->ctx_gz_name), "%s.gz", S->ctx_name);
 }
 
 /* phase (GROM_VERBOSE): the device FASTA loader's times, the teardown's, the footprint */
@@ -1933,12 +1990,18 @@ static int cli_run(int argc, char **argv, int force_serial, int *insert_printed)
     S->t_load = since_process_start();
     fp_sampler fps = {0};
     int ret = cli_parse(S, argc, argv);
-    if (ret < 0) {
+    if (ret < 0 && S->env.vcf_bgzf && (S->one_chrom >= 0 || S->env.vcf_segs)) {
+        /* both depend on plain byte offsets in the rows' file; refused before any file or device is touched */
+        printf("ERROR: GROM_VCF_BGZF cannot be combined with %s: the rows' byte offsets are those of the plain file\n",
+               S->one_chrom >= 0 ? "-c (a -P child)" : "GROM_VCF_SEGS");
+        ret = 1;
+    } else if (ret < 0) {
         ret = 1;
         if (cli_open_bam(S) == 0 && cli_open_fasta(S, &fps) == 0 && cli_candidates(S) == 0) {
             cli_name_outputs(S);
             ret = reads_serially(S) ? run_serial(S) : run_streamed(S);
             cli_report(S, &fps);
+            if (S->gz_failed && ret == 0) ret = 1;
         }
         cli_release(S, &fps);
     }

@@ -515,6 +515,39 @@ int grom_bgzf_check_device(const char *path, int device, int64_t out[8], int64_t
  * host (the lanes as a loop; tests): every load stays inside buf[0, cap) */
 uint32_t grom_bgzf_crc_twin(const uint8_t *buf, int64_t cap, int64_t off, uint32_t n);
 
+/* ---- BGZF written on the device (bgzfwrite.hip; added
+ * within ABI 7: new calls only, GROM_AMD_ABI_VERSION stays 7).  The stream is
+ * cut into payloads of 65280 bytes, each compressed into one BGZF block by a
+ * DEFLATE compressor that runs on `device` (one block per wave); device = -1
+ * runs the compressor's host twin, which writes the same bytes.  A file ends
+ * with the 28-byte EOF marker. ---- */
+typedef struct grom_bgzf_writer grom_bgzf_writer;
+/* A writer of `path` (written under a temporary name, renamed at close) and,
+ * with gzi_path, of bgzip's .gzi index: a little-endian uint64 count, then
+ * one (compressed offset, uncompressed offset) pair of uint64 per block after
+ * the first.  NULL with grom_last_error() set.  GROM_BGZF_PIECE_KB sets the
+ * bytes handed to the device at a time (default 65280 KB, rounded down to
+ * whole payloads); the file does not depend on it. */
+grom_bgzf_writer *grom_bgzf_writer_open(const char *path, int device, const char *gzi_path);
+/* n more bytes of the stream.  The tail under a piece is carried to the next
+ * call: the file depends on the concatenated stream only.  0 or negative */
+int grom_bgzf_writer_write(grom_bgzf_writer *w, const void *buf, int64_t n);
+/* the tail flushed, the EOF marker and the index written, the files renamed,
+ * the writer and its device memory freed (also on failure, which leaves no
+ * file).  out (may be NULL) = {blocks, stored, fixed-Huffman, dynamic-Huffman,
+ * literal-only dynamic-Huffman blocks, input bytes, output bytes, pieces,
+ * device time (us, HIP events; 0 on the host), wall time since open (us)} */
+int grom_bgzf_writer_close(grom_bgzf_writer *w, int64_t out[10]);
+/* the file src compressed to dst and dst.gzi: the writer fed from its pinned
+ * buffers.  out as above */
+int grom_bgzf_compress(const char *src, const char *dst, int device, int64_t out[10]);
+/* Test hook: n_blk payloads buf[offs[i], offs[i + 1]) (offs ascending, each
+ * payload at most 65280 bytes, any start alignment) compressed in one launch;
+ * dst[0, dst_cap) takes the concatenated BGZF blocks, dst_offs[0..n_blk]
+ * their offsets.  dst_cap >= offs[n_blk] - offs[0] + 31 n_blk always fits. */
+int grom_bgzf_blocks(const uint8_t *buf, const int64_t *offs, int64_t n_blk, int device, uint8_t *dst, int64_t dst_cap,
+                     int64_t *dst_offs);
+
 /* ---- the reference FASTA read on the device (fastadev.hip):
  * plain text or BGZF (bgzip); the index (find_genome_length, GROM.c:1321-1428)
  * and the loader (GROM.c:21009-21045) give the host code's results bit for

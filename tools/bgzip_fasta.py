@@ -4,9 +4,12 @@ bytes and the 28-byte EOF block, as `bgzip` writes them.
 
     python tools/bgzip_fasta.py genome.fa            -> genome.fa.gz
     python tools/bgzip_fasta.py genome.fa out.fa.gz -l 6
+    python tools/bgzip_fasta.py genome.fa --device 0    (on the GPU: grom_amd.bgzf_compress, also genome.fa.gz.gzi)
 """
 import argparse
+import os
 import struct
+import sys
 import zlib
 
 PAYLOAD = 65280
@@ -27,8 +30,16 @@ def main():
     ap.add_argument("src")
     ap.add_argument("dst", nargs="?")
     ap.add_argument("-l", "--level", type=int, default=1)
+    ap.add_argument("--device", type=int, default=None, metavar="N",
+                    help="compress on GPU N with the library's DEFLATE kernels (-l does not apply)")
     a = ap.parse_args()
     dst = a.dst or a.src + ".gz"
+    if a.device is not None:
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        import grom_amd
+        st = grom_amd.bgzf_compress(a.src, dst, device=a.device)
+        print(f"{dst}: {st['blocks']} blocks, {st['in_bytes']} -> {st['out_bytes']} bytes on device {a.device}")
+        return
     n = 0
     with open(a.src, "rb") as f, open(dst, "wb") as g:
         while True:
