@@ -22,6 +22,11 @@ HOST_OBJ += build/bgzfdef_host.o
 DEV_OBJ += build/bgzfwrite.o
 DF_HDRS = grom_amd/csrc/bgzfdef.h grom_amd/csrc/bgzfwrite.h grom_amd/csrc/bgzfcrc.h grom_amd/csrc/inflate.h
 
+# a VCF sorted, bgzipped and tabix-indexed on the device: the per-row arithmetic (vcfsort.h, in vcfsort.hip) and its host twin
+HOST_OBJ += build/vcfsort_host.o
+DEV_OBJ += build/vcfsort.o
+VS_HDRS = grom_amd/csrc/vcfsort.h grom_amd/csrc/vcfsort_host.h grom_amd/csrc/bgzfwrite.h grom_amd/csrc/inflate.h
+
 all: $(LIBDIR)/libgrom_amd.so $(BINDIR)/grom $(BINDIR)/grom_synth $(BINDIR)/gromc_binding oracle
 
 build/%.o: grom_amd/csrc/%.c $(HDRS)
@@ -65,6 +70,16 @@ build/bgzfwrite.o: grom_amd/csrc/bgzfwrite.hip $(DF_HDRS) $(HDRS)
 
 # the compressor's host twin (bgzfdef.h's phases, the lanes as loops; no HIP)
 build/bgzfdef_host.o: grom_amd/csrc/bgzfdef_host.cpp $(DF_HDRS) $(HDRS)
+	@mkdir -p build
+	$(CXX) -O2 -g -Wall -fPIC -std=c++17 -c $< -o $@
+
+# the sorting, indexing VCF writer: its kernels, the C calls
+build/vcfsort.o: grom_amd/csrc/vcfsort.hip $(VS_HDRS) $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# its host twin (vcfsort.h's arithmetic in loops, the .tbi through bamio.c's accumulator; no HIP)
+build/vcfsort_host.o: grom_amd/csrc/vcfsort_host.cpp $(VS_HDRS) $(HDRS)
 	@mkdir -p build
 	$(CXX) -O2 -g -Wall -fPIC -std=c++17 -c $< -o $@
 
@@ -132,12 +147,12 @@ oracle:
 # kernel tuning variants, loaded with GROM_AMD_LIB=...:
 #   make variant V=w4 VFLAGS=-DGROM_WAVES_PER_EU=4  ->  grom_amd/lib/variants/libgrom_amd_w4.so
 #   make variant V=q0 VFLAGS=-DGI_QUAD=0            (the inflater's bit reader)
-variant: $(HOST_OBJ) build/sv.o build/baidev.o build/fastadev.o build/gzipdev.o build/bgzfwrite.o
+variant: $(HOST_OBJ) build/sv.o build/baidev.o build/fastadev.o build/gzipdev.o build/bgzfwrite.o build/vcfsort.o
 	@mkdir -p build/variants $(LIBDIR)/variants
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c grom_amd/csrc/scan.hip -o build/variants/scan_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -ffp-contract=off -c grom_amd/csrc/cnv.hip -o build/variants/cnv_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c grom_amd/csrc/ddecode.hip -o build/variants/ddecode_$(V).o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(LIBDIR)/variants/libgrom_amd_$(V).so build/variants/scan_$(V).o build/variants/cnv_$(V).o build/sv.o build/variants/ddecode_$(V).o build/baidev.o build/fastadev.o build/gzipdev.o build/bgzfwrite.o $(HOST_OBJ) -lz -lm
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(LIBDIR)/variants/libgrom_amd_$(V).so build/variants/scan_$(V).o build/variants/cnv_$(V).o build/sv.o build/variants/ddecode_$(V).o build/baidev.o build/fastadev.o build/gzipdev.o build/bgzfwrite.o build/vcfsort.o $(HOST_OBJ) -lz -lm
 
 clean:
 	rm -rf build $(LIBDIR) $(BINDIR)
@@ -235,6 +250,20 @@ $(SANDIR)/deflate_check: tools/deflate_check.cpp $(SANDIR)/bgzfdef_host.o $(SAND
 	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -std=c++17 $(SANFLAGS) $^ -lz -o $@
 
 sanitize: $(SANDIR)/deflate_check
+
+# the sorting, indexing VCF writer's host twin over the tests' grid and the
+# golden VCF, its files read back with zlib: no HIP, no device
+# (tests/test_vcf_tabix_host.py)
+SAN_OBJ += $(SANDIR)/vcfsort_host.o
+$(SANDIR)/vcfsort_host.o: grom_amd/csrc/vcfsort_host.cpp $(VS_HDRS) $(HDRS)
+	@mkdir -p $(SANDIR)
+	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -fPIC -std=c++17 $(SANFLAGS) -c $< -o $@
+
+$(SANDIR)/tbi_check: tools/tbi_check.cpp $(SANDIR)/vcfsort_host.o $(SANDIR)/bgzfdef_host.o $(SANDIR)/bgzfcrc_host.o $(SANDIR)/bamio.o
+	@mkdir -p $(SANDIR)
+	$(CXX) -O1 -g -fno-omit-frame-pointer -Wall -std=c++17 $(SANFLAGS) $^ -lz -lpthread -o $@
+
+sanitize: $(SANDIR)/tbi_check
 
 sanitize: $(SANDIR)/san_driver $(SANDIR)/grom_synth $(SANDIR)/devbuf_check $(SANDIR)/gzip_check
 

@@ -142,6 +142,11 @@ _SIGS = {
     "grom_bgzf_compress": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int64)]),
     "grom_bgzf_blocks": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.c_int64, C.c_int, C.c_char_p, C.c_int64,
                                    C.POINTER(C.c_int64)]),
+    # a VCF sorted, bgzipped and tabix-indexed on the device (vcfsort.hip; device -1: the host twin, vcfsort_host.cpp)
+    "grom_vcf_writer_open": (C.c_void_p, [C.c_char_p, C.c_int]),
+    "grom_vcf_writer_write": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
+    "grom_vcf_writer_close": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "grom_vcf_tabix": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int64)]),
     "grom_upload": (C.c_int, [C.c_int, C.POINTER(Chrom), C.POINTER(Reads), C.POINTER(Chrom), C.POINTER(Reads)]),
     "grom_synth_batch": (C.c_void_p, [C.c_int64, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_uint64,
                                       C.POINTER(Params)]),
@@ -335,6 +340,60 @@ def bgzf_compress(src: str, dst: str, device: "int | None" = None, gzi: bool = T
                 break
             w.write(b)
     return w.stats
+
+
+VCF_TABIX_COUNTERS = ("rows", "header_lines", "contigs", "inversions", "radix_passes", "bins", "chunks",
+                      "linear_windows", "lines_us", "sort_us", "index_us", "wall_us")
+
+
+class VcfWriter:
+    """A VCF written position-sorted, bgzipped and tabix-indexed: `path`,
+    `path`.tbi and `path`.gzi, sorted and indexed on the GPU `device`, or with
+    None by the host twin (the same bytes).  Use as a context manager;
+    `write(bytes)` may cut the stream anywhere.  Everything happens at close;
+    after the block, `stats` holds VCF_TABIX_COUNTERS.  A refused stream (no
+    final newline, a '#' line after a row, fewer than 8 columns, a POS that is
+    not decimal, a row past 2^29) raises with the library's message and leaves
+    no file."""
+
+    def __init__(self, path: str, device: "int | None" = 0):
+        self.path, self.stats = path, None
+        self._h = lib().grom_vcf_writer_open(os.fsencode(path), -1 if device is None else int(device))
+        if not self._h:
+            raise RuntimeError(f"grom_vcf_writer_open failed: {last_error()}")
+
+    def write(self, data: bytes) -> int:
+        if self._h is None:
+            raise ValueError("write to a closed VcfWriter")
+        data = bytes(data)
+        check(lib().grom_vcf_writer_write(self._h, data, len(data)), "grom_vcf_writer_write")
+        return len(data)
+
+    def close(self) -> dict:
+        if self._h is not None:
+            out = (C.c_int64 * 12)()
+            h, self._h = self._h, None
+            rc = lib().grom_vcf_writer_close(h, out)
+            self.stats = dict(zip(VCF_TABIX_COUNTERS, (int(v) for v in out)))
+            check(rc, "grom_vcf_writer_close")
+        return self.stats
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def vcf_tabix(src: str, dst: str, device: "int | None" = 0) -> dict:
+    """The plain VCF `src` as `dst` (BGZF, rows stably sorted by contig in
+    order of first appearance, then POS), `dst`.tbi and `dst`.gzi, on the GPU
+    `device` or with None by the host twin.  Returns VCF_TABIX_COUNTERS."""
+    out = (C.c_int64 * 12)()
+    rc = lib().grom_vcf_tabix(os.fsencode(src), os.fsencode(dst), -1 if device is None else int(device), out)
+    check(rc, "grom_vcf_tabix")
+    return dict(zip(VCF_TABIX_COUNTERS, (int(v) for v in out)))
 
 
 def bgzf_blocks(payloads, device: "int | None" = None, lead: int = 0) -> list:

@@ -803,6 +803,43 @@ static void put64(FILE *f, uint64_t v) {
 
 static uint64_t map_id(void *ctx, int ref, uint64_t v) { (void)ctx; (void)ref; return v; }
 
+/* one reference's bins, pseudo-bin and linear index, as the BAI and the tabix
+ * index both hold them; counts[3] (may be NULL) += {bins, chunks, windows} */
+static void racc_serialise(FILE *f, bai_racc *A, int t, uint64_t (*map)(void *ctx, int ref, uint64_t voff), void *ctx,
+                           int64_t *counts) {
+    if (!A) { put32(f, 0); put32(f, 0); return; }
+    bai_racc_flush(A);
+    qsort(A->bins, A->n_bins, sizeof(bin_acc), cmp_bin_acc);
+    put32(f, (uint32_t)(A->n_bins + (A->any ? 1 : 0)));
+    for (int i = 0; i < A->n_bins; i++) {
+        put32(f, A->bins[i].bin);
+        put32(f, (uint32_t)A->bins[i].n);
+        for (int c = 0; c < A->bins[i].n; c++) {
+            put64(f, map(ctx, t, A->bins[i].c[c].beg));
+            put64(f, map(ctx, t, A->bins[i].c[c].end));
+        }
+        if (counts) { counts[0]++; counts[1] += A->bins[i].n; }
+    }
+    if (A->any) {  /* pseudo-bin 37450: offset span, mapped/unmapped counts */
+        put32(f, 37450u);
+        put32(f, 2u);
+        put64(f, map(ctx, t, A->off_beg));
+        put64(f, map(ctx, t, A->off_end));
+        put64(f, A->n_mapped);
+        put64(f, A->n_unmapped);
+    }
+    /* empty windows take the offset of the window before them
+     * (a smaller offset only makes a query read more) */
+    uint64_t prev = A->n_lin > 0 && A->lin[0] != UINT64_MAX ? A->lin[0] : 0;
+    for (int w = 0; w < A->n_lin; w++) {
+        if (A->lin[w] == UINT64_MAX) A->lin[w] = prev;
+        prev = A->lin[w];
+    }
+    put32(f, (uint32_t)A->n_lin);
+    for (int w = 0; w < A->n_lin; w++) put64(f, map(ctx, t, A->lin[w]));
+    if (counts) counts[2] += A->n_lin;
+}
+
 int bai_write_racc(const char *path, bai_racc **R, int n_ref, uint64_t n_no_coor,
                    uint64_t (*map)(void *ctx, int ref, uint64_t voff), void *ctx) {
     if (!map) map = map_id;
@@ -810,40 +847,25 @@ int bai_write_racc(const char *path, bai_racc **R, int n_ref, uint64_t n_no_coor
     if (!f) return -1;
     fwrite("BAI\1", 1, 4, f);
     put32(f, (uint32_t)n_ref);
-    for (int t = 0; t < n_ref; t++) {
-        bai_racc *A = R[t];
-        if (!A) { put32(f, 0); put32(f, 0); continue; }
-        bai_racc_flush(A);
-        qsort(A->bins, A->n_bins, sizeof(bin_acc), cmp_bin_acc);
-        put32(f, (uint32_t)(A->n_bins + (A->any ? 1 : 0)));
-        for (int i = 0; i < A->n_bins; i++) {
-            put32(f, A->bins[i].bin);
-            put32(f, (uint32_t)A->bins[i].n);
-            for (int c = 0; c < A->bins[i].n; c++) {
-                put64(f, map(ctx, t, A->bins[i].c[c].beg));
-                put64(f, map(ctx, t, A->bins[i].c[c].end));
-            }
-        }
-        if (A->any) {  /* pseudo-bin 37450: offset span, mapped/unmapped counts */
-            put32(f, 37450u);
-            put32(f, 2u);
-            put64(f, map(ctx, t, A->off_beg));
-            put64(f, map(ctx, t, A->off_end));
-            put64(f, A->n_mapped);
-            put64(f, A->n_unmapped);
-        }
-        /* empty windows take the offset of the window before them
-         * (a smaller offset only makes a query read more) */
-        uint64_t prev = A->n_lin > 0 && A->lin[0] != UINT64_MAX ? A->lin[0] : 0;
-        for (int w = 0; w < A->n_lin; w++) {
-            if (A->lin[w] == UINT64_MAX) A->lin[w] = prev;
-            prev = A->lin[w];
-        }
-        put32(f, (uint32_t)A->n_lin);
-        for (int w = 0; w < A->n_lin; w++) put64(f, map(ctx, t, A->lin[w]));
-    }
+    for (int t = 0; t < n_ref; t++) racc_serialise(f, R[t], t, map, ctx, NULL);
     put64(f, n_no_coor);
     return fclose(f) != 0 ? -1 : 0;
+}
+
+int tbi_write_racc(FILE *f, bai_racc **R, int n_ref, const char *names, int32_t l_nm, int64_t counts[3]) {
+    fwrite("TBI\1", 1, 4, f);
+    put32(f, (uint32_t)n_ref);
+    put32(f, 2u);           /* format: VCF */
+    put32(f, 1u);           /* col_seq */
+    put32(f, 2u);           /* col_beg */
+    put32(f, 0u);           /* col_end */
+    put32(f, (uint32_t)'#');  /* meta */
+    put32(f, 0u);           /* skip */
+    put32(f, (uint32_t)l_nm);
+    if (l_nm > 0) fwrite(names, 1, (size_t)l_nm, f);
+    for (int t = 0; t < n_ref; t++) racc_serialise(f, R[t], t, map_id, NULL, counts);
+    put64(f, 0);            /* n_no_coor */
+    return ferror(f) ? -1 : 0;
 }
 
 int bai_build(const char *bam_path) {

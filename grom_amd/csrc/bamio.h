@@ -202,6 +202,12 @@ int bai_racc_set_linear(bai_racc *A, const uint64_t *lin, int32_t n_lin);
 /* R[t] may be NULL (no records); 0 or -1 */
 int bai_write_racc(const char *path, bai_racc **R, int n_ref, uint64_t n_no_coor,
                    uint64_t (*map)(void *ctx, int ref, uint64_t voff), void *ctx);
+/* the tabix index (.tbi, uncompressed) of a VCF written to f: the header
+ * (format 2, columns 1 / 2 / 0, meta '#', skip 0), the n_ref NUL-terminated
+ * names (l_nm bytes in all), each reference as bai_write_racc serialises it,
+ * n_no_coor = 0.  counts[3] (may be NULL) += {bins, chunks, linear windows}.
+ * The caller BGZF-compresses the bytes.  0 or -1 */
+int tbi_write_racc(FILE *f, bai_racc **R, int n_ref, const char *names, int32_t l_nm, int64_t counts[3]);
 /* parse an index file; 0, or -1 */
 int bai_load(const char *bai_path, bai_index *idx);
 void bai_free(bai_index *idx);

@@ -18,6 +18,14 @@ int df_host_blocks(const uint8_t *buf, const int64_t *offs, int64_t n_blk, uint8
 /* the code-length builder alone (bgzfdef.h, df_build_lengths): n <= 288 */
 void df_host_lengths(const uint32_t *freq, int n, int limit, int force_two, uint8_t *len);
 
+
+/* Internal (vcfsort.hip): the stream written so far flushed as if at close,
+ * then coff[0, n_blk) = every block's offset in the file and coff[n_blk] =
+ * the offset the EOF marker will have.  Only close may follow.  The number of
+ * blocks, or a negative GROM_E_* code (cap < n_blk + 1: GROM_E_ARG). */
+struct grom_bgzf_writer;
+int64_t grom_bgzf_writer_block_offsets(struct grom_bgzf_writer *w, int64_t *coff, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

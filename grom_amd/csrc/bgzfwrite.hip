@@ -527,6 +527,20 @@ extern "C" int grom_bgzf_writer_close(grom_bgzf_writer *w, int64_t out[10]) {
     return rc;
 }
 
+extern "C" int64_t grom_bgzf_writer_block_offsets(grom_bgzf_writer *w, int64_t *coff, int64_t cap) {
+    if (!w || !coff) return GROM_E_ARG;
+    w->flush();
+    w->finish_flying();
+    if (w->failed) {
+        grom_set_last_error(w->err);
+        return w->failed;
+    }
+    if (cap < w->n_blk + 1) return GROM_E_ARG;
+    for (int64_t i = 0; i < w->n_blk; i++) coff[i] = i == 0 ? 0 : (int64_t)w->index[(size_t)(2 * (i - 1))];
+    coff[w->n_blk] = w->out_bytes;
+    return w->n_blk;
+}
+
 extern "C" int grom_bgzf_compress(const char *src, const char *dst, int device, int64_t out[10]) {
     if (out) memset(out, 0, 10 * sizeof(int64_t));
     char m[4600];

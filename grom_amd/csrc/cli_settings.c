@@ -27,6 +27,8 @@ void cli_settings_read(cli_settings *s) {
     s->serial_decode = num("GROM_SERIAL_DECODE", 0) > 0; /* the serial BAM reader */
     s->build_index = num("GROM_BUILD_INDEX", 0) != 0;    /* a missing BAM index is built on the device */
     s->vcf_bgzf = num("GROM_VCF_BGZF", 0) != 0;          /* the rows and the CTX file written as BGZF on the device */
+    s->vcf_tabix = num("GROM_VCF_TABIX", 0) != 0;        /* ... position-sorted, with a tabix index (implies BGZF) */
+    if (s->vcf_tabix) s->vcf_bgzf = 1;
     s->device_decode = num("GROM_DEVICE_DECODE", -1);    /* 0: BAM decode on host threads */
     s->fasta_device = num("GROM_FASTA_DEVICE", -1); /* 0: a BGZF -r on the host; 1: a plain -r on the device */
     s->dump = getenv("GROM_DUMP");                  /* test hook: counter dumps, named after this prefix */

@@ -17,6 +17,7 @@ typedef struct {
     int serial_decode;                /* set above 0 */
     int build_index;                  /* set and not 0 */
     int vcf_bgzf;                     /* set and not 0 */
+    int vcf_tabix;                    /* set and not 0; sets vcf_bgzf */
     int device_decode, fasta_device;  /* -1 unset, else the number given (0 and 1 are tested) */
     /* the text given, NULL when unset */
     const char *dump, *vcf_segs, *ctx_raw, *chroms, *filedate;

@@ -293,9 +293,10 @@ typedef struct {
     int one_chrom, sub_child, sub_start, sub_end;
     char part_name[4096];
     /* GROM_VCF_BGZF: the rows and the CTX file go out as BGZF (<name>.gz),
-     * compressed on the run's first device; what each close reported */
+     * compressed on the run's first device; what each close reported
+     * (GROM_VCF_TABIX: through the sorting, indexing writer, out[12]) */
     char gz_name[4100], ctx_gz_name[4100];
-    int64_t gz_rows[10], gz_ctx[10];
+    int64_t gz_rows[12], gz_ctx[12];
     int gz_failed;
 } cli_state;
 
@@ -920,22 +921,24 @@ static int passes_length(const cli_state *S, const chrom_plan *c) {
  * frees its device memory, and keeps its counters in out[10] */
 typedef struct {
     grom_bgzf_writer *w;
+    grom_vcf_writer *vw; /* GROM_VCF_TABIX: the sorting, indexing writer instead */
     cli_state *S;
     int64_t *out;
 } gz_cookie;
 
 static ssize_t gz_cookie_write(void *c, const char *buf, size_t n) {
     gz_cookie *g = c;
-    if (grom_bgzf_writer_write(g->w, buf, (int64_t)n) != 0) { g->S->gz_failed = 1; return 0; }
+    const int rc = g->vw ? grom_vcf_writer_write(g->vw, buf, (int64_t)n) : grom_bgzf_writer_write(g->w, buf, (int64_t)n);
+    if (rc != 0) { g->S->gz_failed = 1; return 0; }
     return (ssize_t)n;
 }
 
 static int gz_cookie_close(void *c) {
     gz_cookie *g = c;
-    const int rc = grom_bgzf_writer_close(g->w, g->out);
+    const int rc = g->vw ? grom_vcf_writer_close(g->vw, g->out) : grom_bgzf_writer_close(g->w, g->out);
     if (rc != 0) {
         g->S->gz_failed = 1;
-        printf("Error writing BGZF output: %s\n", grom_last_error());
+        printf("Error writing %s output: %s\n", g->vw ? "sorted, indexed VCF" : "BGZF", grom_last_error());
     }
     free(g);
     return rc ? -1 : 0;
@@ -948,11 +951,17 @@ static FILE *gz_fopen(cli_state *S, const char *name, int with_gzi, int64_t *out
     gz_cookie *g = calloc(1, sizeof(*g));
     g->S = S;
     g->out = out;
-    g->w = grom_bgzf_writer_open(name, S->device, with_gzi ? gzi : NULL);
-    if (!g->w) { free(g); return NULL; }
+    if (S->env.vcf_tabix) g->vw = grom_vcf_writer_open(name, S->device);
+    else g->w = grom_bgzf_writer_open(name, S->device, with_gzi ? gzi : NULL);
+    if (!g->w && !g->vw) { free(g); return NULL; }
     const cookie_io_functions_t io = {NULL, gz_cookie_write, NULL, gz_cookie_close};
     FILE *f = fopencookie(g, "w", io);
-    if (!f) { grom_bgzf_writer_close(g->w, NULL); free(g); return NULL; }
+    if (!f) {
+        if (g->vw) grom_vcf_writer_close(g->vw, NULL);
+        else grom_bgzf_writer_close(g->w, NULL);
+        free(g);
+        return NULL;
+    }
     setvbuf(f, NULL, _IOFBF, 1 << 20);
     return f;
 }
@@ -992,7 +1001,14 @@ static void finish_outputs(cli_state *S, textbuf *ctx_all) {
         ctx_postpass(ctx_all->p, ctx_all->len, &S->hdr, S->P.insert_max_size, S->P.lseq, S->P.vcf == 1, ctx);
         fclose(ctx);
     }
-    if (S->env.vcf_bgzf && !S->gz_failed)
+    if (S->env.vcf_tabix && !S->gz_failed)
+        printf("Sorted, indexed output (device %d): %s with %s.tbi and %s.gzi, %lld rows on %lld contigs, %lld inversions, "
+               "%lld radix passes, %lld bins; %s with its .tbi and .gzi, %lld rows on %lld contigs; %.3f s on the device\n",
+               S->device, S->gz_name, S->gz_name, S->gz_name, (long long)S->gz_rows[0], (long long)S->gz_rows[2],
+               (long long)S->gz_rows[3], (long long)S->gz_rows[4], (long long)S->gz_rows[5], S->ctx_gz_name,
+               (long long)S->gz_ctx[0], (long long)S->gz_ctx[2],
+               (double)(S->gz_rows[8] + S->gz_rows[9] + S->gz_rows[10] + S->gz_ctx[8] + S->gz_ctx[9] + S->gz_ctx[10]) / 1e6);
+    else if (S->env.vcf_bgzf && !S->gz_failed)
         printf("BGZF output (device %d): %s with %s.gzi, %lld blocks, %lld -> %lld bytes; %s, %lld blocks, %lld -> %lld bytes; "
                "%.3f s on the device\n", S->device, S->gz_name, S->gz_name, (long long)S->gz_rows[0], (long long)S->gz_rows[5],
                (long long)S->gz_rows[6], S->ctx_gz_name, (long long)S->gz_ctx[0], (long long)S->gz_ctx[5],
@@ -1990,7 +2006,14 @@ static int cli_run(int argc, char **argv, int force_serial, int *insert_printed)
     S->t_load = since_process_start();
     fp_sampler fps = {0};
     int ret = cli_parse(S, argc, argv);
-    if (ret < 0 && S->env.vcf_bgzf && (S->one_chrom >= 0 || S->env.vcf_segs)) {
+    if (ret < 0 && S->env.vcf_tabix && (S->one_chrom >= 0 || S->env.vcf_segs || S->P.vcf != 1)) {
+        /* a child's rows have no header, the segments are byte ranges of the unsorted file, tab rows are not VCF */
+        printf("ERROR: GROM_VCF_TABIX cannot be combined with %s\n",
+               S->one_chrom >= 0 ? "-c (a -P child): its rows are a part of a file"
+               : S->env.vcf_segs ? "GROM_VCF_SEGS: the rows' byte offsets are those of the plain, unsorted file"
+                                 : "-f: tab-separated rows are not VCF");
+        ret = 1;
+    } else if (ret < 0 && S->env.vcf_bgzf && (S->one_chrom >= 0 || S->env.vcf_segs)) {
         /* both depend on plain byte offsets in the rows' file; refused before any file or device is touched */
         printf("ERROR: GROM_VCF_BGZF cannot be combined with %s: the rows' byte offsets are those of the plain file\n",
                S->one_chrom >= 0 ? "-c (a -P child)" : "GROM_VCF_SEGS");

@@ -548,6 +548,33 @@ int grom_bgzf_compress(const char *src, const char *dst, int device, int64_t out
 int grom_bgzf_blocks(const uint8_t *buf, const int64_t *offs, int64_t n_blk, int device, uint8_t *dst, int64_t dst_cap,
                      int64_t *dst_offs);
 
+/* ---- a VCF written position-sorted, bgzipped and tabix-indexed on the
+ * device (vcfsort.hip; added within ABI 7: new calls only,
+ * GROM_AMD_ABI_VERSION stays 7).  The writer collects the whole stream (the
+ * sort is global), and at close sorts the rows stably by (contig in order of
+ * first appearance, POS) on `device`, writes them behind the header through
+ * the BGZF writer above and builds the tabix index from the blocks' offsets:
+ * `path`, `path`.tbi and `path`.gzi, written under temporary names and
+ * renamed.  device = -1 runs the host twin, which writes the same three files
+ * byte for byte.  Refused with GROM_E_ARG and a message, no file left behind:
+ * a last line without a newline, a '#' line after the first row, a row with
+ * fewer than 8 columns, a POS that is not decimal, a row that ends past 2^29
+ * (the .tbi limit, 512 Mb).  GROM_VCF_CHUNK_KB sets the size of the pinned
+ * chunks the stream is collected in (default 32768); the files do not depend
+ * on it. ---- */
+typedef struct grom_vcf_writer grom_vcf_writer;
+grom_vcf_writer *grom_vcf_writer_open(const char *path, int device);
+/* n more bytes of the stream, cut anywhere (a line's tail is carried) */
+int grom_vcf_writer_write(grom_vcf_writer *w, const void *buf, int64_t n);
+/* everything above; the writer and its device memory freed (also on failure).
+ * out (may be NULL) = {rows, header lines, contigs, inversions found in the
+ * input (rows below the row before them), radix passes run, bins, chunks,
+ * linear windows, device time (us, HIP events; 0 on the host) of lines and
+ * facts, of sort and gather, of the index, wall time since open (us)} */
+int grom_vcf_writer_close(grom_vcf_writer *w, int64_t out[12]);
+/* the plain VCF src through the writer to dst, dst.tbi and dst.gzi */
+int grom_vcf_tabix(const char *src_plain_vcf, const char *dst, int device, int64_t out[12]);
+
 /* ---- the reference FASTA read on the device (fastadev.hip):
  * plain text or BGZF (bgzip); the index (find_genome_length, GROM.c:1321-1428)
  * and the loader (GROM.c:21009-21045) give the host code's results bit for
